@@ -1,8 +1,15 @@
 #!/usr/bin/env python3
 """bench.py -- rendered-objects/sec of the geometric hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+A plain run measures the headline only: it builds the scene, runs W warm-up steps, times K steps and prints the JSON line
+(`value`, `ms_per_step`, the kernel timings of the timed region and the rooflines derived from them).  Everything else below
+-- the textural leg, the secondary meshes, K1, the real meshes, the host-issue time, the ALU roofline, the blocking exchange,
+configs[2] / [4], compositing and the CPU baselines -- runs with --full.  --dump-outputs DIR writes what the last timed step
+computed (the maps a caller receives -- gathered over the ranks when N > 1 -- and the gradients of the pose / FFD parameters)
+as DIR/<name>.npy in float32; the inputs are seeded, so two builds can be compared output for output.
 
 One STEP = one VKITTI frame's worth of objects (16, the cap of geometric/scripts/main.py:812) per GPU, each object
 going through exactly what one iteration of the reference's test-time optimisation loop does
@@ -15,8 +22,8 @@ every dataset are absent on the benchmark box (sdn_hip/synth.py).  Inputs are re
 region; nothing leaves the device inside it.  With N > 1 the objects are sharded over the ranks (weak scaling: 16 per
 GPU) and the rendered maps are exchanged with ONE RCCL all_gather per step, the only exchange this path has.
 
-The second half of BASELINE.json's metric, "textural-GAN fwd+bwd ms at 375x1242", is measured right after on the same
-GPU(s): one Pix2PixHDModel.train_step (textural/train.py:69-95 -- G + E forward, three multiscale-D forwards, generator
+The second half of BASELINE.json's metric, "textural-GAN fwd+bwd ms at 375x1242", is measured with --full, right after, on
+the same GPU(s): one Pix2PixHDModel.train_step (textural/train.py:69-95 -- G + E forward, three multiscale-D forwards, generator
 and discriminator backward, two Adam updates) at batch 4, 384x1248 (375x1242 padded to a multiple of 16),
 48-channel generator input, 3-scale discriminator, no VGG loss (its weights cannot be downloaded here).  Reported as
 `textural_gan_fwd_bwd_ms` with its own roofline object.
@@ -904,7 +911,16 @@ def main():
     ap.add_argument('--share-gpu', action='store_true',
                     help='development aid, never a measurement: all N ranks use cuda:0 and talk over gloo -- the sharded code '
                          'paths with the real kernels on a box with one GPU')
+    ap.add_argument('--full', action='store_true',
+                    help='everything besides the headline: the textural leg, secondary meshes, K1, real meshes, host-issue '
+                         'time, the ALU roofline, the blocking exchange, configs[2] / [4], compositing, CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed (maps, parameter gradients) as DIR/<name>.npy (float32)')
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit('bench.py: --steps must be at least 1')
+    if args.skip_geometric and not args.full:
+        raise SystemExit('bench.py: --skip-geometric leaves only the textural leg, which runs with --full')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher of N ranks
@@ -948,7 +964,7 @@ def main():
     line = {}
     if not args.skip_geometric:
         line.update(geometric_leg(args, device, world, rank))
-    if not args.skip_textural:
+    if args.full and not args.skip_textural:
         tsteps = args.textural_steps or max(1, min(args.steps, 5))
         tex = textural_leg(device, tsteps, 1, world)
         line['textural_gan_fwd_bwd_ms'] = tex['ms_per_step']
@@ -965,7 +981,7 @@ def main():
                 line['textural_extras'] = {'error': repr(e)}
     else:
         line['textural_gan_fwd_bwd_ms'] = None
-    if world == 1 and not args.no_extras and not args.skip_geometric:
+    if world == 1 and args.full and not args.no_extras and not args.skip_geometric:
         try:
             line['compositing'] = compositing_numbers(device, not args.no_cpu_baseline)
         except Exception as e:
@@ -975,7 +991,7 @@ def main():
                 line[key] = derender3d_loop(device, mesh=mesh)
             except Exception as e:
                 line[key] = {'error': repr(e)}
-    if not args.no_extras and not args.skip_geometric and not args.skip_textural:
+    if args.full and not args.no_extras and not args.skip_geometric and not args.skip_textural:
         try:   # configs[4] runs at every N (frames sharded by rank, one all_gather)
             line['edit_pipeline'] = edit_pipeline(device, world, rank)
         except Exception as e:
@@ -985,7 +1001,7 @@ def main():
     if args.share_gpu:
         line['share_gpu'] = 'development run: %d ranks on ONE GPU over gloo -- not a measurement' % world
     if rank == 0:
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             for key, fn in (('cpu_baseline', cpu_baseline), ('cpu_baseline_textural', cpu_baseline_textural)):
                 if (key == 'cpu_baseline' and args.skip_geometric) or (key != 'cpu_baseline' and args.skip_textural):
                     continue
@@ -1093,6 +1109,25 @@ def real_meshes_leg(args, device, rank):
     return out
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6
+
+
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: every tensor of `arrays` as out_dir/<name>.npy in float32, so that two builds can be compared output
+    for output.  When they hold more than DUMP_BUDGET_BYTES in all (the gathered maps of many ranks), each is replaced by a
+    fixed, seeded sample of its flattened elements (sorted positions, the same for the same shape) of a proportional size."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.size for a in arrays.values()) * 4
+    keep = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if keep < 1.0:
+            idx = np.sort(np.random.default_rng(seed).integers(0, a.size, int(a.size * keep)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def geometric_leg(args, device, world, rank):
     import sdn_hip
     bank, sizes, cls, params, targets, ptf = build_scene(device, seed=1234 + rank, mesh=HEADLINE_MESH)
@@ -1128,11 +1163,14 @@ def geometric_leg(args, device, world, rank):
             pending[0] = None
             return out
 
+    extras = args.full and not args.no_extras and world == 1
     for _ in range(args.warmup):
         full_step()
     drain()
-    issue_ms = host_issue_ms(full_step)
-    drain()
+    issue_ms = None
+    if args.full:
+        issue_ms = host_issue_ms(full_step)
+        drain()
     if world > 1:
         dist.barrier()
     sdn_hip.timing_enable(True)
@@ -1140,9 +1178,11 @@ def geometric_leg(args, device, world, rank):
         sdn_hip.timing_read_slot(slot)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for _ in range(args.steps - 1):
         full_step()
-    drain()
+    last = full_step()
+    if ex is not None:
+        last = drain()   # a step returns the PREVIOUS step's exchange: the last step's gathered maps
     enqueue = time.perf_counter() - t0   # host time to issue the steps (the GPU runs behind it)
     torch.cuda.synchronize()
     if world > 1:
@@ -1150,10 +1190,19 @@ def geometric_leg(args, device, world, rank):
     elapsed = time.perf_counter() - t0
     fwd_ms, fwd_n, _ = sdn_hip.timing_read_slot(sdn_hip.SLOT_RASTER_TILES)
     bwd_ms, bwd_n, _ = sdn_hip.timing_read_slot(sdn_hip.SLOT_EDGE_SCAN)
+    if args.dump_outputs and rank == 0:
+        # outside the timed region, before anything below runs the step again (the gradients are those of the last step)
+        if ex is None:
+            out = {'mask': last[0], 'normal': last[1], 'depth': last[2]}
+        else:
+            out = {'maps_' + payload: last}
+        out.update(('grad_' + k, p.grad) for k, p in params.items() if p.grad is not None)
+        dump_outputs(args.dump_outputs, out)
+    del last
     # ---- N > 1: what ONE exchange costs when nothing overlaps it (outside the timed region): says whether the step or the
     # exchange bounds the headline, and whether RCCL ran the all_gather direct or through a ring (DESIGN section 4's budget)
     exchange = None
-    if ex is not None:
+    if ex is not None and args.full:
         sdn_hip.timing_enable(False)
         maps = step().detach()
         torch.cuda.synchronize()
@@ -1178,7 +1227,7 @@ def geometric_leg(args, device, world, rank):
     # ---- the same frame step on the OTHER template family (outside the headline's timed region): since r04 the headline runs on
     # the templates with the reference's CAD statistics, the smoother car_like family is the secondary number
     cad = None
-    if not getattr(args, 'no_extras', False) and world == 1:
+    if extras:
         try:
             cbank, csizes, ccls, cparams, ctargets, cptf = build_scene(device, seed=4321 + rank, mesh=SECONDARY_MESH)
             cstep = make_step(device, cbank, ccls, cparams, ctargets, cptf, backward=not args.forward_only, pack=False)
@@ -1208,7 +1257,7 @@ def geometric_leg(args, device, world, rank):
     # ---- the SAME headline frame step under the reference's DEFAULT coverage rule K1 (scripts/env.sh:11 exports
     # NEURAL_RENDERER_UNSAFE=1 -> rasterize.py:102-236): what a reference user's environment selects
     k1 = None
-    if not getattr(args, 'no_extras', False) and world == 1:
+    if extras:
         try:
             import neural_renderer as nr
             nr.use_unsafe_rasterizer(True)
@@ -1235,7 +1284,7 @@ def geometric_leg(args, device, world, rank):
     # ---- the same frame step on the reference's OWN six ShapeNet templates: the synthetic family is fitted to
     # their statistics, these are the meshes themselves
     real = None
-    if not getattr(args, 'no_extras', False) and world == 1:
+    if extras:
         try:
             real = real_meshes_leg(args, device, rank)
         except Exception as e:
@@ -1307,29 +1356,30 @@ def geometric_leg(args, device, world, rank):
     # ALU view of the forward rasterizer: the counting build of the kernel tallies the pixel tests of one
     # more step, outside the timed region; flops per test are counted from csrc/raster_math.h (inside_ndc: 3 edges x
     # (4 sub + 2 mul + 1 compare) = 21; a covered pixel adds barycentric weights 23 + perspective depth 6 = 29)
-    try:
-        from sdn_hip import ops
-        fwd_step = make_step(device, bank, cls, params, targets, ptf, backward=False)
-        with ops.verification(count_work=True):
-            with torch.no_grad():
-                fwd_step()
-        cand, passed, keys = ops.last_work()
-        flops = 21.0 * cand + 29.0 * passed
-        sec = fwd_ms / 1e3 / max(fwd_n, 1)
-        line['roofline_alu'] = {'bound': 'valu fp32', 'kernel': 'k_raster_tiles', 'candidate_pixel_tests': cand,
-                                'tests_passed': passed, 'depth_keys': keys, 'flops_per_launch': flops,
-                                'achieved': flops / sec / 1e12 if fwd_n else 0.0, 'peak': 157.3, 'unit': 'TFLOP/s',
-                                'frac': flops / sec / 1e12 / 157.3 if fwd_n else 0.0,
-                                'pixel_tests_per_s': cand / sec if fwd_n else 0.0,
-                                'note': 'counted flops are a few per cent of the fp32 vector peak, yet the kernel ISSUES vector-ALU '
-                                        'instructions ~84 %% of its cycles at 66 %% lane utilisation (SQ counters of the r05 tree, '
-                                        'profiles/r05v_pmcgeo_sq1.json / _sq2.json: 148.0 M vector wave-instructions per launch = 119 per '
-                                        '64-candidate pass all in; the wave-shared box loop itself is ~35 in the ISA: index arithmetic, table '
-                                        'reads, three edge tests, depth cull, hit-queue bookkeeping) '
-                                        'for 21 counted flops per test; ~%.0f candidate tests per covered pixel' % (
-                                            cand / max(1.0, per_launch * 0.4 * S * S))}
-    except Exception as e:
-        line['roofline_alu'] = {'error': repr(e)}
+    if args.full:
+        try:
+            from sdn_hip import ops
+            fwd_step = make_step(device, bank, cls, params, targets, ptf, backward=False)
+            with ops.verification(count_work=True):
+                with torch.no_grad():
+                    fwd_step()
+            cand, passed, keys = ops.last_work()
+            flops = 21.0 * cand + 29.0 * passed
+            sec = fwd_ms / 1e3 / max(fwd_n, 1)
+            line['roofline_alu'] = {'bound': 'valu fp32', 'kernel': 'k_raster_tiles', 'candidate_pixel_tests': cand,
+                                    'tests_passed': passed, 'depth_keys': keys, 'flops_per_launch': flops,
+                                    'achieved': flops / sec / 1e12 if fwd_n else 0.0, 'peak': 157.3, 'unit': 'TFLOP/s',
+                                    'frac': flops / sec / 1e12 / 157.3 if fwd_n else 0.0,
+                                    'pixel_tests_per_s': cand / sec if fwd_n else 0.0,
+                                    'note': 'counted flops are a few per cent of the fp32 vector peak, yet the kernel ISSUES vector-ALU '
+                                            'instructions ~84 %% of its cycles at 66 %% lane utilisation (SQ counters of the r05 tree, '
+                                            'profiles/r05v_pmcgeo_sq1.json / _sq2.json: 148.0 M vector wave-instructions per launch = 119 per '
+                                            '64-candidate pass all in; the wave-shared box loop itself is ~35 in the ISA: index arithmetic, table '
+                                            'reads, three edge tests, depth cull, hit-queue bookkeeping) '
+                                            'for 21 counted flops per test; ~%.0f candidate tests per covered pixel' % (
+                                                cand / max(1.0, per_launch * 0.4 * S * S))}
+        except Exception as e:
+            line['roofline_alu'] = {'error': repr(e)}
     bwd = roof('k_edge_scan_sil + k_edge_rows + k_chunk_sum (one event pair)', ['sum', 'sdn::k_edge_scan_sil', 'sdn::k_edge_rows', 'sdn::k_chunk_sum'],
                bwd_bytes, bwd_ms, bwd_n,
                'silhouette edge gradient (K5): owners filed per row by the scan kernel, rows evaluated from LDS; algorithmic '

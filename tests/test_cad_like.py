@@ -9,7 +9,6 @@ import os
 import sys
 
 import numpy as np
-import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (ROOT, os.path.join(ROOT, 'tools'), os.path.join(ROOT, 'tests'), os.path.join(ROOT, '3d-sdn_amd')):
@@ -54,15 +53,24 @@ def test_cad_like_matches_the_measured_statistics():
     assert c['depth_complexity'] < 0.5 * pooled['depth_complexity'] and c['area_px_p99'] < 0.3 * pooled['area_px_p99']
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference/geometric/assets'), reason='needs the reference checkout')
 def test_stored_statistics_are_what_the_assets_give():
+    """The mesh is loaded from the reference's assets where they exist, else taken from tests/golden/cad_templates.npz (the
+    same ShapenetObj vertices + faces, recorded by tests/golden/make_cad_golden_hi.py --templates)."""
     import cad_mesh_stats as cs
-    from derender3d.models import ShapenetObj
     ref = json.load(open(STATS))
     key, want = next(iter(ref['per_mesh'].items()))
     cls = key.split('/')[0]
-    oid = [d for d in os.listdir(os.path.join('/root/reference/geometric/assets', cls)) if d.startswith(key.split('/')[1])][0]
-    o = ShapenetObj(cls, oid, root_dir='/root/reference/geometric/assets')
-    got = cs.mesh_stats(o.vertices.numpy(), o.faces.numpy())
+    from oracle.build_ref import REF_ROOT
+    assets = os.path.join(REF_ROOT, 'geometric', 'assets')
+    if os.path.isdir(assets):
+        from derender3d.models import ShapenetObj
+        oid = [d for d in os.listdir(os.path.join(assets, cls)) if d.startswith(key.split('/')[1])][0]
+        o = ShapenetObj(cls, oid, root_dir=assets)
+        verts, faces = o.vertices.numpy(), o.faces.numpy()
+    else:
+        z = np.load(os.path.join(ROOT, 'tests', 'golden', 'cad_templates.npz'))
+        j = [i for i, m in enumerate(z['meshes']) if str(m).split('/')[1].startswith(key.split('/')[1])][0]
+        verts, faces = z['t%d/verts' % j], z['t%d/faces' % j]
+    got = cs.mesh_stats(verts, faces)
     for k in ('triangles', 'depth_complexity', 'area_px_median', 'area_px_p99'):
         assert abs(got[k] - want[k]) <= 1e-6 * max(1.0, abs(want[k])), k

@@ -1,5 +1,11 @@
 """Shared helpers of the test-suite (input generators, comparison utilities)."""
+import hashlib
+import json
+import os
+
 import numpy as np
+
+REF_DIGESTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'ref_digests.json')
 
 
 def random_soup(rng, bs, nf, scale, zlo=0.5, zhi=5.0):
@@ -17,6 +23,18 @@ def bits(a):
 
 def biteq(a, b):
     return a.shape == b.shape and np.array_equal(bits(a), bits(b))
+
+
+def digest(a):
+    """dtype, shape and sha256 of the bytes of `a`: equal digests <=> biteq (up to the hash) with an array not at hand."""
+    a = np.ascontiguousarray(a)
+    return '%s %s %s' % (a.dtype.str, 'x'.join(map(str, a.shape)), hashlib.sha256(a.tobytes()).hexdigest())
+
+
+def recorded_digests():
+    """tests/golden/ref_digests.json: digests of the reference's outputs (tests/golden/make_ref_digests.py)."""
+    with open(REF_DIGESTS) as f:
+        return json.load(f)
 
 
 def posed_mesh(verts, faces, theta=0.6, scale=(3.9, 1.5, 1.6), translation=(2.0, 1.0, -12.0), focal=725.0,

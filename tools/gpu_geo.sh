@@ -7,5 +7,5 @@ mkdir -p $O
 cd $R
 timeout 900 python -m pytest tests -m gpu -x -q > $O/${TAG}_tests.log 2>&1; echo "tests exit $?" >> $O/${TAG}_tests.log
 tail -5 $O/${TAG}_tests.log
-timeout 600 python bench.py --steps 20 --warmup 3 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
+timeout 600 python bench.py --full --steps 20 --warmup 3 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err
 cat $O/${TAG}_bench.json

@@ -14,13 +14,13 @@ W=$1; shift
 case $W in
 baseline)
   timeout 1500 python -m pytest tests -m gpu -q --tb=short -rf -p no:cacheprovider -x > $O/lab_tests.log 2>&1; tail -3 $O/lab_tests.log
-  timeout 600 python bench.py --skip-textural --no-cpu-baseline > $O/lab_bench_geo.json 2> $O/lab_bench_geo.err; cut -c1-300 $O/lab_bench_geo.json
+  timeout 600 python bench.py --full --skip-textural --no-cpu-baseline > $O/lab_bench_geo.json 2> $O/lab_bench_geo.err; cut -c1-300 $O/lab_bench_geo.json
   timeout 600 python tools/tile_stats.py cad_like real:0 real:1 real:2 real:3 real:4 real:5 > $O/lab_tile_stats.log 2>&1; tail -5 $O/lab_tile_stats.log ;;
 tex)
   timeout 900 python -m pytest tests/test_gpu_textural_fullsize.py -m gpu -q --tb=short -rf -p no:cacheprovider -k "batch4" -s > $O/lab_tests.log 2>&1
   grep -E "passed|failed|batch-4|batch 4|D\(3" $O/lab_tests.log | head
   SDN_WGRAD_STREAM=0 SDN_D_STREAMS=0 timeout 400 python tests/gpu_layer_times.py > $O/lab_layer_times_serial.log 2>&1; grep -E "^totals|^====" $O/lab_layer_times_serial.log
-  timeout 600 python bench.py --skip-geometric --no-cpu-baseline --no-extras > $O/lab_bench_tex.json 2> $O/lab_bench_tex.err; cut -c1-400 $O/lab_bench_tex.json ;;
+  timeout 600 python bench.py --full --skip-geometric --no-cpu-baseline --no-extras > $O/lab_bench_tex.json 2> $O/lab_bench_tex.err; cut -c1-400 $O/lab_bench_tex.json ;;
 raster-sweep)
   timeout 900 python -m pytest tests/test_gpu_raster.py tests/test_gpu_renderer.py tests/test_gpu_cad_golden.py tests/test_gpu_k1_coverage.py tests/test_gpu_derender3d.py tests/test_gpu_dropin.py -m gpu -q --tb=short -rf -p no:cacheprovider > $O/lab_tests.log 2>&1; tail -3 $O/lab_tests.log
   ( for M in cad_like car_like real:2 real; do
@@ -33,7 +33,7 @@ raster-sweep)
 update-ab)
   timeout 900 python -m pytest tests/test_gpu_trainstep.py -m gpu -q --tb=short -rf -p no:cacheprovider > $O/lab_tests.log 2>&1; tail -3 $O/lab_tests.log
   for U in 1 0 1 0; do
-    SDN_UPDATE_STREAM=$U timeout 600 python bench.py --skip-geometric --no-cpu-baseline --no-extras --textural-steps 8 > $O/lab_bench_tex_u$U.json 2> /dev/null
+    SDN_UPDATE_STREAM=$U timeout 600 python bench.py --full --skip-geometric --no-cpu-baseline --no-extras --textural-steps 8 > $O/lab_bench_tex_u$U.json 2> /dev/null
     echo "SDN_UPDATE_STREAM=$U $(cut -c1-60 $O/lab_bench_tex_u$U.json)"
   done ;;
 head-race)
@@ -45,7 +45,7 @@ whead)
 whead-ab)
   timeout 1200 python -m pytest tests/test_gpu_trainstep.py tests/test_gpu_textural_fullsize.py tests/test_gpu_encoder.py -m gpu -q --tb=short -rf -p no:cacheprovider > $O/lab_tests.log 2>&1; tail -5 $O/lab_tests.log
   for U in 0 1 2 0 1 2; do
-    SDN_WGRAD_HEAD=$U timeout 600 python bench.py --skip-geometric --no-cpu-baseline --no-extras --textural-steps 8 > $O/lab_bench_tex_wh$U.json 2> /dev/null
+    SDN_WGRAD_HEAD=$U timeout 600 python bench.py --full --skip-geometric --no-cpu-baseline --no-extras --textural-steps 8 > $O/lab_bench_tex_wh$U.json 2> /dev/null
     echo "SDN_WGRAD_HEAD=$U $(cut -c1-60 $O/lab_bench_tex_wh$U.json)"
   done ;;
 timeline)

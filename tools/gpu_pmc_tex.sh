@@ -7,7 +7,7 @@ mkdir -p $O
 cd /tmp; export TMPDIR=/tmp
 for C in "TCC_HIT_sum TCC_MISS_sum" "FETCH_SIZE" "WRITE_SIZE"; do
   N=$(echo $C | tr ' ' '_')
-  timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/pmc_$N -o t -- python $R/bench.py --no-cpu-baseline --skip-geometric --textural-steps 1 > $O/${TAG}_pmc_$N.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --pmc $C --output-format csv -d /tmp/pmc_$N -o t -- python $R/bench.py --full --no-cpu-baseline --skip-geometric --textural-steps 1 > $O/${TAG}_pmc_$N.log 2>&1
   python $R/tools/pmc_summary.py /tmp/pmc_$N k_conv > $O/${TAG}_pmc_tex_$N.json
 done
 python - <<PY
