@@ -775,3 +775,45 @@ class L1LossFn(torch.autograd.Function):
             raise RuntimeError('L1LossFn: empty_like did not keep the operands\' layout')
         check(lib().sdn_l1_loss_bwd(ptr(_dense_flat(a)), ptr(_dense_flat(b)), a.numel(), ptr(g), ptr(fga), ptr(fgb), stream()))
         return ga, gb
+
+
+def edit_assemble(base_segm, edit_inst, obj_label, obj_pose, code_ids, codes, pose_channels=1):
+    """The textural inputs of F edited frames in one launch (textural/edit_vkitti.py:62-103, edit_benchmark.py:87-126;
+    csrc/fast_edit.hip).  base_segm [1 | F, 1, H, W] fp32 (one source label map for all frames, or one per frame),
+    edit_inst [F, 1, H, W] uint8 raw object ids, obj_label / obj_pose [F, 256] int32 tables by raw id, code_ids [K] int32
+    ascending, codes [C, K] fp32.  Returns (segm [F,1,H,W], inst [F,1,H,W], pose [F,pose_channels,H,W], feat [F,C,H,W],
+    missing [F] int32): fp32 maps -- Pix2PixHDModel.encode_input converts label and pose to indices itself -- and, per
+    frame, the number of pixels whose instance has no code (painted 0).  Nothing is copied to the host."""
+    base_segm = _f32(base_segm, 'base_segm')
+    edit_inst = want(edit_inst, torch.uint8, 'edit_inst')
+    obj_label = want(obj_label, torch.int32, 'obj_label')
+    obj_pose = want(obj_pose, torch.int32, 'obj_pose')
+    code_ids = want(code_ids, torch.int32, 'code_ids')
+    codes = _f32(codes, 'codes')
+    if edit_inst.dim() != 4 or edit_inst.shape[1] != 1:
+        raise ValueError('edit_inst must be [F, 1, H, W], got %s' % (tuple(edit_inst.shape),))
+    F, _, H, W = edit_inst.shape
+    if base_segm.dim() != 4 or tuple(base_segm.shape[1:]) != (1, H, W) or base_segm.shape[0] not in (1, F):
+        raise ValueError('base_segm must be [1 or %d, 1, %d, %d], got %s' % (F, H, W, tuple(base_segm.shape)))
+    if tuple(obj_label.shape) != (F, 256) or tuple(obj_pose.shape) != (F, 256):
+        raise ValueError('obj_label and obj_pose must be [%d, 256]' % F)
+    if code_ids.dim() != 1 or codes.dim() != 2 or codes.shape[1] != code_ids.shape[0] or code_ids.numel() < 1:
+        raise ValueError('code_ids must be [K] and codes [C, K], got %s and %s' % (tuple(code_ids.shape), tuple(codes.shape)))
+    if pose_channels not in (1, 2):
+        raise ValueError('pose_channels must be 1 (binned pose) or 2 (feat_pose_num_bins == 0)')
+    dev = edit_inst.device
+    for t, name in ((base_segm, 'base_segm'), (obj_label, 'obj_label'), (obj_pose, 'obj_pose'), (code_ids, 'code_ids'),
+                    (codes, 'codes')):
+        if t.device != dev:
+            raise ValueError('%s is on %s, edit_inst on %s' % (name, t.device, dev))
+    C, K = codes.shape
+    with torch.cuda.device(dev):   # the stream handed over is this device's current one
+        segm = torch.empty(F, 1, H, W, dtype=torch.float32, device=dev)
+        inst = torch.empty(F, 1, H, W, dtype=torch.float32, device=dev)
+        pose = torch.empty(F, pose_channels, H, W, dtype=torch.float32, device=dev)
+        feat = torch.empty(F, C, H, W, dtype=torch.float32, device=dev)
+        missing = torch.empty(F, dtype=torch.int32, device=dev)
+        check(lib().sdn_edit_assemble(ptr(base_segm), 0 if base_segm.shape[0] == 1 and F > 1 else H * W, ptr(edit_inst),
+                                      ptr(obj_label), ptr(obj_pose), ptr(code_ids), ptr(codes), K, C, F, H * W, pose_channels,
+                                      ptr(segm), ptr(inst), ptr(pose), ptr(feat), ptr(missing), stream()))
+    return segm, inst, pose, feat, missing

@@ -301,3 +301,79 @@ def assemble_item(opt, params, segm, image, inst=None, pose_inst=None, pose_json
     if getattr(opt, 'feat_depth', None):
         out['depth'] = depth_feature(depth, opt, params, depth_wrap_int16) if depth is not None else torch.zeros_like(A)
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the edit path: textural/edit_vkitti.py:62-103, edit_benchmark.py:87-126
+EDIT_CLASS_LABEL = {1: 2, 2: 12}   # class_id of NNNNN.json -> label id (car, van), edit_vkitti.py:79
+
+
+def edit_tables(opt, edit_json):
+    """The two per-frame look-up tables of sdn_edit_assemble, built on the host from one NNNNN.json: (obj_label, obj_pose),
+    int32 [256] indexed by raw object id.  obj_label[k] = {1: 2, 2: 12}[class_id] (0: k is not in the JSON),
+    obj_pose[k] = np.digitize(alpha / pi, bins) (edit_vkitti.py:73-82; 0 without pose bins).  compositing.frame_json
+    numbers objects from 1 and NNNNN.png holds uint8, so a key outside 1..255 is refused; an unknown class_id raises
+    KeyError as the reference's dict look-up does."""
+    nb = opt.feat_pose_num_bins
+    bins = pose_bins(nb) if nb else None
+    label = np.zeros(256, dtype=np.int32)
+    pose = np.zeros(256, dtype=np.int32)
+    for key, rec in edit_json.items():
+        k = int(key)
+        if not 1 <= k <= 255:
+            raise ValueError('object id %d of the edit JSON is outside 1..255' % k)
+        label[k] = EDIT_CLASS_LABEL[rec['class_id']]
+        if nb:
+            pose[k] = int(np.digitize(rec['alpha'] / pi, bins))
+    return label, pose
+
+
+def assemble_edit(opt, params, base_item, edit_inst_u8, edit_json, codes, normal_u8=None):
+    """The generator inputs of EDITED frames (the `for` body of edit_vkitti.py:62-103 / edit_benchmark.py:87-126) in one
+    kernel launch, with the source frame's appearance codes painted at each instance's new pixels on the device.
+      base_item     assemble_item's dict of the SOURCE frame (both *_precomputed_path options set: label + 1, car pixels
+                    without an instance already "misc"), or a list of F such dicts (one source per frame, edit_benchmark)
+      edit_inst_u8  uint8 [1, H, W] raw object ids of NNNNN.png (compositing.wire_tensors), or a list of F of them
+      edit_json     the frame's NNNNN.json dict {object id: {'class_id', 'alpha', ...}}, or a list of F
+      codes         (ids, means [K, feat_num]) of Encoder.feat_table on the source frame
+      normal_u8     uint8 [3, H, W] of NNNNN-normal.png, None ("no cars"), or a list of F of either
+    Returns a dict of batched tensors: label / inst [F,1,h,w], pose [F,1|2,h,w], feat [F,feat_num,h,w] (fp32: what
+    Pix2PixHDModel.fake_inference takes), normal [F,3,h,w] (transform(normal) + 1/255, zeros where absent or without
+    --feat_normal), missing int32 [F] (pixels whose instance has no source code; they are painted 0) -- all on the device,
+    nothing is read back -- and obj_label / obj_pose, the host-built int32 [F, 256] tables."""
+    from sdn_hip import ops as _ops
+    many = isinstance(edit_inst_u8, (list, tuple))
+    insts = list(edit_inst_u8) if many else [edit_inst_u8]
+    F = len(insts)
+    jsons = list(edit_json) if many else [edit_json]
+    normals = list(normal_u8) if isinstance(normal_u8, (list, tuple)) else [normal_u8] * F
+    bases = list(base_item) if isinstance(base_item, (list, tuple)) else [base_item]
+    if F < 1 or len(jsons) != F or len(normals) != F or len(bases) not in (1, F):
+        raise ValueError('assemble_edit: %d instance maps, %d JSON records, %d normal maps, %d source items'
+                         % (F, len(jsons), len(normals), len(bases)))
+    tables = [edit_tables(opt, js) for js in jsons]
+    obj_label = np.stack([t[0] for t in tables])
+    obj_pose = np.stack([t[1] for t in tables])
+    ids, means = codes
+    for t in insts + [b['label'] for b in bases] + [ids, means]:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('assemble_edit expects torch tensors')
+        if not t.is_cuda:   # as every op of this project: no host path
+            raise NotImplementedError('assemble_edit: a tensor is on %s; the edit assembly only runs on the GPU' % t.device)
+    dev = insts[0].device
+    edit = torch.stack([_geometry(t, opt, params, 'nearest') for t in insts])
+    base = torch.stack([b['label'] for b in bases]).float()
+    label, inst, pose, feat, missing = _ops.edit_assemble(
+        base, edit, torch.from_numpy(obj_label).to(dev), torch.from_numpy(obj_pose).to(dev), ids.to(torch.int32),
+        means.t().contiguous(), pose_channels=1 if opt.feat_pose_num_bins else 2)
+    zero = None
+    nrm = []
+    for n in normals:
+        if n is not None and opt.feat_normal:
+            nrm.append(transform(n, opt, params) + 1 / 255)   # "bias caused by 0..256 instead 0..255" (edit_vkitti.py:93)
+        else:
+            if zero is None:
+                zero = torch.zeros(3, label.shape[2], label.shape[3], dtype=torch.float32, device=dev)
+            nrm.append(zero)
+    return {'label': label, 'inst': inst, 'pose': pose, 'feat': feat, 'missing': missing, 'normal': torch.stack(nrm),
+            'obj_label': obj_label, 'obj_pose': obj_pose}

@@ -343,14 +343,15 @@ class Encoder(nn.Module, _Fused):
             inst[i] = inst[i] * bs + i
         return inst
 
-    def _pooled(self, input, inst):
+    def _pooled(self, input, inst, with_counts=False):
         feats = self._chain('model', self.model, self.input_nc)(input)[0]          # [N, C, H, W]
         inst = self._disambiguate(inst)
-        ids, inverse = torch.unique(inst.reshape(-1).long(), return_inverse=True)  # one sync for the id count
+        ids, inverse, *counts = torch.unique(inst.reshape(-1).long(), return_inverse=True,
+                                             return_counts=with_counts)            # one sync for the id count
         N, C, H, W = feats.shape
         seg = inverse.to(torch.int32).reshape(N, H, W)
         out, means = _ops.SegmentMeanFn.apply(feats.contiguous(), seg, int(ids.numel()))
-        return out, ids, means
+        return (out, ids, means, counts[0]) if with_counts else (out, ids, means)
 
     def forward(self, input, inst):
         out, _, _ = self._pooled(input, inst)
@@ -360,6 +361,13 @@ class Encoder(nn.Module, _Fused):
         _, ids, means = self._pooled(input, inst)
         table = means.t().detach().cpu().tolist()
         return {int(i): [float(v) for v in row] for i, row in zip(ids.cpu().tolist(), table)}
+
+    def feat_table(self, input, inst):
+        """What generate_feat_dict reports, left on the device: (ids int64 [K] ascending, means [K, output_nc],
+        counts int64 [K] pixels per id).  The table an edit paints onto the edited frames (textural/edit.py; the reference
+        goes through the host dict, edit_vkitti.py:57, 97-103)."""
+        _, ids, means, counts = self._pooled(input, inst, with_counts=True)
+        return ids, means.t().detach().contiguous(), counts
 
 
 class NLayerDiscriminator(nn.Module, _Fused):

@@ -2,7 +2,7 @@
 (/root/reference/textural/models/pix2pixHD_model.py), same method names and loss list.
 
 What is kept: `initialize(opt)`, `encode_input`, `discriminate`, `forward` -> [[G_GAN, G_GAN_Feat, G_VGG, D_real, D_fake,
-G_L1, E_VAE, E_regress], fake_image|None], `fake_inference`, `inference`, `get_edges`, `save`,
+G_L1, E_VAE, E_regress], fake_image|None], `fake_inference`, `inference`, `encode_features`, `get_edges`, `save`,
 `update_learning_rate`, `update_fixed_params`; `optimizer_G` / `optimizer_D` (Adam, lr 2e-4, betas (beta1, 0.999));
 the input assembly (one-hot labels + instance edges + encoded features + one-hot pose + normals, :124-166).
 What changes: every network is a textural.models.networks module running on libsdn_hip.so; tensors are created on the
@@ -351,6 +351,36 @@ class Pix2PixHDModel(BaseModel):
                 for k in range(self.opt.feat_num):
                     feat_map[0, k][mask] = float(row[k])
         return feat_map
+
+    def encode_features(self, image, inst):
+        """pix2pixHD_model.py:320-341, the producer of the cluster file `sample_features` reads: {label: ndarray
+        [n, feat_num + 1]} for every label < label_nc (empty where unused), one row per instance id i of `inst` under
+        label = i if i < 5000 else i // 5000 -- the encoder's feature at the instance's median pixel and, last, the
+        instance's pixel count / (h * w // 32).  The encoder's output is constant over an instance, so the feature at the
+        median pixel IS the instance's mean: both columns come from `Encoder.feat_table`, with one copy to the host,
+        instead of a nonzero() per instance.  Two differences: an id whose label is >= label_nc gets its own entry (the
+        reference's dict look-up raises KeyError), and only batch size 1 is taken (what the reference's feature script
+        feeds).  CPU tensors raise NotImplementedError."""
+        for t, name in ((image, 'image'), (inst, 'inst')):
+            if not t.is_cuda:
+                raise NotImplementedError('%s is on %s; encode_features only runs on the GPU' % (name, t.device))
+        if inst.dim() != 4 or inst.shape[0] != 1:
+            raise ValueError('encode_features takes one frame: inst [1, 1, h, w], got %s' % (tuple(inst.shape),))
+        feat_num = self.opt.feat_num
+        h, w = inst.shape[2], inst.shape[3]
+        block_num = 32
+        with torch.no_grad():
+            ids, means, counts = self.netE.feat_table(image.detach(), inst.clone())
+        table = torch.cat((means.double(), counts.double()[:, None], ids.double()[:, None]), dim=1).cpu().numpy()
+        feature = {i: np.zeros((0, feat_num + 1)) for i in range(self.opt.label_nc)}
+        for row in table:
+            i, num = int(row[feat_num + 1]), int(row[feat_num])
+            label = i if i < 5000 else i // 5000
+            val = np.zeros((1, feat_num + 1))
+            val[0, :feat_num] = row[:feat_num]
+            val[0, feat_num] = float(num) / (h * w // block_num)
+            feature[label] = np.append(feature.get(label, np.zeros((0, feat_num + 1))), val, axis=0)
+        return feature
 
     # ------------------------------------------------------------------------------------------------ bookkeeping
     def save(self, which_epoch):

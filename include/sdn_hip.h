@@ -68,10 +68,10 @@ const char* sdn_last_error(void);
 /* The ABI revision this header describes.  It is raised whenever an entry point gains / loses an argument OR a caller-owned
  * buffer changes its required size behind an unchanged signature (r04: the `key` / `acc` scratch of
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
- * with 40 ints, sdn_render_maps_bwd takes bg).  A binding
+ * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added).  A binding
  * must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise
  * (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 8
+#define SDN_ABI_VERSION 9
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -385,7 +385,9 @@ int sdn_avgpool_global(const float* x, int N, int HW, int C, float* out, int bac
  * segment ids in [0, K) (ids are unique across the batch, as after networks.py:313-316).  sums [C, K] and counts [K] are
  * caller-owned scratch that is also the result table (sums[c, k] / counts[k] = mean feature of segment k, what
  * generate_feat_dict reports, :327-346); out [N, C, HW] = the mean of each pixel's segment.  The backward pass is the
- * same call on the incoming gradient. */
+ * same call on the incoming gradient.  With K <= 4096 and K <= HW the sums are added in a fixed order (the same input
+ * gives the same bits on every call); `out` then serves as scratch for the partial sums before it is written and must not
+ * alias x.  Larger tables are summed with float atomics, in arrival order. */
 int sdn_segment_mean(const float* x, const int32_t* seg, int N, int C, int HW, int K, float* sums, float* counts,
                      float* out, sdnStream stream);
 
@@ -455,6 +457,26 @@ int sdn_pose_params_bwd(const float* theta, const float* scales, const float* g_
 int sdn_composite_frame(const float* masks, const float* normals, const float* depth_maps, const float* zooms, int n,
                         int R, const int32_t* objs, int m, const int32_t* bounds, const int32_t* kk8, const double* kkf,
                         int H, int W, float* inst, float* nrm, float* dep, sdnStream stream);
+
+/* ---- textural inputs of F edited frames in one launch: textural/edit_vkitti.py:62-103, edit_benchmark.py:87-126 ------------
+ * base_segm [1 | F, HW] fp32: the SOURCE frame's label map as the loader leaves it with both *_precomputed_path options
+ * (+1 applied, car pixels without an instance already "misc": edit_vkitti.py:50-53); base_stride 0 shares one source among
+ * the F frames (edit_vkitti), HW gives each frame its own (edit_benchmark).  edit_inst [F, HW] uint8: the raw object ids of
+ * NNNNN.png.  obj_label / obj_pose [F, 256] int32: per-frame tables indexed by raw object id, built by the caller from
+ * NNNNN.json -- label {1: 2, 2: 12}[class_id] (0 = id not in the JSON), pose np.digitize(alpha / pi, bins).
+ * Per pixel, with s = base label (2 / 12 -> 5) and k = raw id:  k in the JSON: segm = obj_label[k], inst = 1000 k,
+ * pose = obj_pose[k];  otherwise segm = s, inst = (k == 0 ? s : k), pose = 0.  (Raw ids are <= 255 < 1000, so the
+ * reference's sequential in-place rewrites never alias and this table form is exact.)
+ * feat[f, c, p] = codes[c, row], row = position of the pixel's final instance id in code_ids (int32 [K], ascending -- the
+ * unique ids of the source's instance map) and codes [C, K] the source's mean feature per id (sdn_segment_mean's table).
+ * An id without a code paints 0 in all C channels and counts the pixel in missing[f] (int32 [F], cleared by the call).
+ * pose_channels: 1 (binned pose) or 2 (feat_pose_num_bins == 0: the reference allocates two channels and writes neither,
+ * so both are zero).  Outputs are dense fp32: segm_out, inst_out [F, 1, HW], pose_out [F, pose_channels, HW],
+ * feat_out [F, C, HW].  Kpad + C K <= 12288 (Kpad = K rounded up to a power of two): the tables live in LDS. */
+int sdn_edit_assemble(const float* base_segm, long base_stride, const uint8_t* edit_inst, const int32_t* obj_label,
+                      const int32_t* obj_pose, const int32_t* code_ids, const float* codes, int K, int C, int F, int HW,
+                      int pose_channels, float* segm_out, float* inst_out, float* pose_out, float* feat_out,
+                      int32_t* missing, sdnStream stream);
 
 /* ---- PerspectiveTransform: derender3d/models/transforms.py:102-158, all objects of a frame at once -----------------------
  * out[b,v] = zoom( shear( R(quat[b]) (verts[b,v] * scales[b]) + trans[b] ) ),  shear: x -= x0/z0 * z, y -= y0/z0 * z with
