@@ -817,3 +817,95 @@ def edit_assemble(base_segm, edit_inst, obj_label, obj_pose, code_ids, codes, po
                                       ptr(obj_label), ptr(obj_pose), ptr(code_ids), ptr(codes), K, C, F, H * W, pose_channels,
                                       ptr(segm), ptr(inst), ptr(pose), ptr(feat), ptr(missing), stream()))
     return segm, inst, pose, feat, missing
+
+
+SCENE_RGB, SCENE_MASK, SCENE_IGNORE = 1, 2, 4   # `kinds` of sdn_scene_crops
+
+
+def scene_cover(masks):
+    """Cover words of N BINARY maps (csrc/scene_crops.hip): masks [N, 1, H, W] fp32, every value exactly 0.0 or 1.0 (what
+    Mask R-CNN delivers; verified only with SDN_DEBUG_CHECKS=1 in the environment, which makes the call synchronous) ->
+    uint32 words as an int32 tensor [ceil(N / 32), H, W]: bit (n & 31) of word n // 32 is set where map n is.  Nothing is
+    copied to the host."""
+    masks = _f32(masks, 'masks')
+    if masks.dim() != 4 or masks.shape[1] != 1 or masks.shape[0] < 1:
+        raise ValueError('masks must be [N, 1, H, W] with N >= 1, got %s' % (tuple(masks.shape),))
+    N, _, H, W = masks.shape
+    with torch.cuda.device(masks.device):
+        cover = torch.empty((N + 31) // 32, H, W, dtype=torch.int32, device=masks.device)
+        check(lib().sdn_scene_cover(ptr(masks), N, H, W, ptr(cover), stream()))
+    return cover
+
+
+def scene_crops(kinds, rois_host, tables, H, W, image_size, mask_size, frame_u8=None, cover=None, ignore_cover=None, nearer=None,
+                mean=(0.5, 0.5, 0.5), std=(0.25, 0.25, 0.25)):
+    """All per-object crops of one frame in one launch (sdn_scene_crops; geometric/scripts/main.py:365-373, 418-421 with
+    derender3d/datasets.py:49-71, 141-172): crop_square + PIL bilinear resize + to_tensor (+ Normalize for the image), bit
+    for bit.  kinds: a sum of SCENE_RGB (needs frame_u8 uint8 [3, H, W]), SCENE_MASK (needs cover = scene_cover(masks);
+    the masks must be binary) and SCENE_IGNORE (needs ignore_cover and nearer int64 [N, ceil(N / 32)]).  rois_host: numpy
+    int32 [N, 4] = (y0, x0, y1, x1); tables = (objs [N, 12], bounds, kk8) int32 CUDA tensors as
+    derender3d.scene.crop_tables prepares them.  Returns (rgbs [N,3,S_i,S_i], masks [N,1,S_m,S_m], ignores [N,1,S_m,S_m]),
+    None for a kind not asked for.  Nothing is copied to the host."""
+    rois_host = np.ascontiguousarray(rois_host, dtype=np.int32)
+    if rois_host.ndim != 2 or rois_host.shape[1] != 4:
+        raise ValueError('rois must be [N, 4], got %s' % (rois_host.shape,))
+    N = rois_host.shape[0]
+    objs, bounds, kk8 = (want(t, torch.int32, name) for t, name in zip(tables, ('objs', 'bounds', 'kk8')))
+    if tuple(objs.shape) != (N, 12):
+        raise ValueError('objs must be [%d, 12] for %d rois, got %s' % (N, N, tuple(objs.shape)))
+    dev = objs.device
+    chunks = (N + 31) // 32
+    if kinds & SCENE_RGB:
+        frame_u8 = want(frame_u8, torch.uint8, 'frame_u8')
+        if frame_u8 is None or tuple(frame_u8.shape) != (3, H, W):
+            raise ValueError('frame_u8 must be uint8 [3, %d, %d]' % (H, W))
+    if kinds & SCENE_MASK:
+        cover = want(cover, torch.int32, 'cover')
+    if kinds & SCENE_IGNORE:
+        ignore_cover = want(ignore_cover, torch.int32, 'ignore_cover')
+    for t, name, need in ((cover, 'cover', kinds & SCENE_MASK), (ignore_cover, 'ignore_cover', kinds & SCENE_IGNORE)):
+        if need and (t is None or tuple(t.shape) != (chunks, H, W)):
+            raise ValueError('%s must be the int32 [%d, %d, %d] tensor of scene_cover for %d objects' % (name, chunks, H, W, N))
+    if kinds & SCENE_IGNORE:
+        nearer = want(nearer, torch.int64, 'nearer')
+        if nearer is None or tuple(nearer.shape) != (N, chunks):
+            raise ValueError('nearer must be int64 [%d, %d]' % (N, chunks))
+    with torch.cuda.device(dev):
+        rgbs = torch.empty(N, 3, image_size, image_size, device=dev) if kinds & SCENE_RGB else None
+        masks = torch.empty(N, 1, mask_size, mask_size, device=dev) if kinds & SCENE_MASK else None
+        ignores = torch.empty(N, 1, mask_size, mask_size, device=dev) if kinds & SCENE_IGNORE else None
+        check(lib().sdn_scene_crops(ptr(frame_u8) if kinds & SCENE_RGB else None, ptr(cover) if kinds & SCENE_MASK else None,
+                                    ptr(ignore_cover) if kinds & SCENE_IGNORE else None, ptr(nearer) if kinds & SCENE_IGNORE else None,
+                                    rois_host.ctypes.data, ptr(objs), ptr(bounds), ptr(kk8), N, H, W, image_size, mask_size, kinds,
+                                    float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
+                                    ptr(rgbs), ptr(masks), ptr(ignores), stream()))
+    return rgbs, masks, ignores
+
+
+def scene_edit(theta_deltas, translation2ds, log_depths, mroi_norms, droi_norms, interests, records):
+    """F edit lists applied to one de-rendered scene in one launch (sdn_scene_edit; geometric/scripts/main.py:481-514).
+    theta_deltas, translation2ds, mroi_norms, droi_norms [N, 2], log_depths [N, 1] fp32, interests uint8 [N], records int32
+    [F, P, 8] (derender3d.scene.edit_records), all CUDA.  Returns (theta_deltas [F,N,2], translation2ds [F,N,2], log_depths
+    [F,N,1], interests uint8 [F,N]), bit-equal to the reference's element-wise torch statements.  Nothing is copied to the
+    host."""
+    th, tr, ld, mr, dr = (_f32(t, name) for t, name in ((theta_deltas, 'theta_deltas'), (translation2ds, 'translation2ds'),
+                                                        (log_depths, 'log_depths'), (mroi_norms, 'mroi_norms'),
+                                                        (droi_norms, 'droi_norms')))
+    interests = want(interests, torch.uint8, 'interests')
+    records = want(records, torch.int32, 'records')
+    N = th.shape[0]
+    if N < 1 or any(tuple(t.shape) != (N, 2) for t in (th, tr, mr, dr)) or ld.numel() != N or interests.numel() != N:
+        raise ValueError('scene_edit: theta_deltas, translation2ds, mroi_norms, droi_norms must be [N, 2], log_depths [N, 1], '
+                         'interests [N]; got %s' % ([tuple(t.shape) for t in (th, tr, ld, mr, dr, interests)],))
+    if records.dim() != 3 or records.shape[2] != 8 or records.shape[0] < 1:
+        raise ValueError('records must be int32 [F, P, 8], got %s' % (tuple(records.shape),))
+    F, P = records.shape[0], records.shape[1]
+    dev = th.device
+    with torch.cuda.device(dev):
+        o_th = torch.empty(F, N, 2, device=dev)
+        o_tr = torch.empty(F, N, 2, device=dev)
+        o_ld = torch.empty(F, N, 1, device=dev)
+        o_in = torch.empty(F, N, dtype=torch.uint8, device=dev)
+        check(lib().sdn_scene_edit(ptr(th), ptr(tr), ptr(ld), ptr(mr), ptr(dr), ptr(interests), ptr(records) if P else None, F, N,
+                                   P, ptr(o_th), ptr(o_tr), ptr(o_ld), ptr(o_in), stream()))
+    return o_th, o_tr, o_ld, o_in

@@ -68,10 +68,11 @@ const char* sdn_last_error(void);
 /* The ABI revision this header describes.  It is raised whenever an entry point gains / loses an argument OR a caller-owned
  * buffer changes its required size behind an unchanged signature (r04: the `key` / `acc` scratch of
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
- * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added).  A binding
+ * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
+ * sdn_scene_edit added).  A binding
  * must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise
  * (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 9
+#define SDN_ABI_VERSION 10
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -477,6 +478,42 @@ int sdn_edit_assemble(const float* base_segm, long base_stride, const uint8_t* e
                       const int32_t* obj_pose, const int32_t* code_ids, const float* codes, int K, int C, int F, int HW,
                       int pose_channels, float* segm_out, float* inst_out, float* pose_out, float* feat_out,
                       int32_t* missing, sdnStream stream);
+
+/* ---- the geometric branch's inputs from a frame and the detector's output: geometric/scripts/main.py:365-373, 405-421 with
+ * derender3d/datasets.py:49-71 (Transforms.crop_square) and :141-172 (BaseDataset.transform_rgb / _mask / _ignore) ----------
+ * The reference crops, resizes (PIL bilinear) and converts on the host, three PIL round trips per object.  Three entries:
+ *
+ * sdn_scene_cover: masks [N, H W] fp32, BINARY (exactly 0 or 1: what Mask R-CNN delivers; checked only when the environment
+ * holds SDN_DEBUG_CHECKS=1, which makes the call synchronous) -> cover uint32 [ceil(N / 32), H W]: bit (n & 31) of word
+ * n / 32 is set where object n's mask is.  Also used for caller-supplied ignore maps (main.py:416). */
+int sdn_scene_cover(const float* masks, int N, int H, int W, uint32_t* cover, sdnStream stream);
+/* sdn_scene_crops: one launch for all N objects.  kinds: 1 image crops, 2 mask crops, 4 ignore crops (any sum).
+ *   rgbs    [N, 3, image_size, image_size]  from frame uint8 [3, H, W], outside the frame 127,
+ *           value ((u8 / 255) - mean[c]) / std[c] in three fp32 operations (to_tensor, Normalize)
+ *   masks   [N, 1, mask_size, mask_size]    from bit n of `cover`, outside 0, value u8 / 255
+ *   ignores [N, 1, mask_size, mask_size]    slot n = ((ignore_cover & nearer[n]) != 0) * 255, outside 255, value u8 / 255;
+ *           nearer int64 [N, ceil(N / 32)] (low 32 bits used): the objects whose union is slot n's map (main.py:407-414:
+ *           those sorted before position n), or bit n alone when ignore_cover holds caller-supplied maps
+ * Per object exactly crop_square -> PIL resize -> to_tensor: the window of side s = max(h, w) at
+ * (roi[0] - (s - h) / 2, roi[1] - (s - w) / 2); crop_square pads right / bottom by max(0, roi end + d - size) only, so when
+ * s - w (s - h) is odd the window's last column (row) lies beyond the padded image and PIL's crop makes it 0 -- reproduced.
+ * rois_host: HOST int32 [N, 4] = (y0, x0, y1, x1), read before the launch for validation (an empty roi, or a window whose
+ * filter does not fit the 32 KiB row tile, is SDN_EINVAL).  objs: DEVICE int32 [N, 12] rows (window y, x, s, x limit, y limit
+ * of the padded image, then for image_size and for mask_size: first row of `bounds`, first element of `kk8`, ksize -- 0 when
+ * s equals the output size and Pillow skips the resampling -- and one unused int); bounds / kk8 as for sdn_composite_frame. */
+int sdn_scene_crops(const uint8_t* frame, const uint32_t* cover, const uint32_t* ignore_cover, const int64_t* nearer,
+                    const int32_t* rois_host, const int32_t* objs, const int32_t* bounds, const int32_t* kk8, int N, int H, int W,
+                    int image_size, int mask_size, int kinds, float mean0, float mean1, float mean2, float std0, float std1,
+                    float std2, float* rgbs, float* masks, float* ignores, sdnStream stream);
+/* ---- F edit lists applied to one de-rendered scene: geometric/scripts/main.py:481-514 ------------------------------------------
+ * theta_deltas, translation2ds, mroi_norms, droi_norms [N, 2], log_depths [N, 1], interests uint8 [N].  records: DEVICE int32
+ * [F, P, 8] rows (object index or -1 for an unused slot, type 0 delete / 1 modify, then as float bits: new centre row, column,
+ * 2 log(zoom), cos(-ry), sin(-ry); one unused int), in the reference's iteration order.  Outputs [F, N, ...]: copies, and per
+ * record  translation2d = (centre - mroi) / droi,  log_depth -= 2 log zoom,  theta_delta = (c cos - s sin, s cos + c sin);
+ * delete clears interests_out[f, n].  A later record of the same object reads what the earlier one left. */
+int sdn_scene_edit(const float* theta_deltas, const float* translation2ds, const float* log_depths, const float* mroi_norms,
+                   const float* droi_norms, const uint8_t* interests, const int32_t* records, int F, int N, int P,
+                   float* theta_out, float* translation_out, float* log_depth_out, uint8_t* interests_out, sdnStream stream);
 
 /* ---- PerspectiveTransform: derender3d/models/transforms.py:102-158, all objects of a frame at once -----------------------
  * out[b,v] = zoom( shear( R(quat[b]) (verts[b,v] * scales[b]) + trans[b] ) ),  shear: x -= x0/z0 * z, y -= y0/z0 * z with
