@@ -11,6 +11,8 @@ ten element-wise launches per operation.  Here the crops of all objects are one 
 pre-pass sdn_scene_cover), F edit lists are one launch (sdn_scene_edit) and one render of the stacked [F N] blob; the host
 prepares only what is host data anyway (rois, Pillow's resampling tables, the JSON).  `SceneSession` is the counterpart of
 textural/edit.py's `EditSession`: `SceneSession(...).edit(lists)` -> frames -> `EditSession(...).render_batch(frames)`.
+`SceneSession.from_detections` starts from the detector's heads (maskrcnn/detections.py, sdn_unmold_masks) and
+`SceneSession.from_scene_gt` from a ground-truth instance image (sdn_scene_gt_masks; main.py:724-761).
 
 Two quirks of the reference are kept on purpose (parity is the contract):
   * crop_square pads the right / bottom by max(0, roi end + d - size) although its window ends one pixel further when
@@ -174,6 +176,24 @@ def ignore_crops(plan, cover, log_depths=None, droi_norms=None, pairing='referen
                            ignore_cover=icover, nearer=nearer)[2]
 
 
+def scene_gt_inputs(scene_u8, codes):
+    """main.py:745-746 for K objects in one launch: (masks float32 [K, 1, H, W] CUDA, rois numpy int32 [K, 4], areas numpy
+    int32 [K]) of an instance-colour image scene_u8 uint8 [H, W, 3] CUDA and K colour codes [K, 3] (host sequence or CUDA
+    uint8).  One device-to-host copy (5 K integers).  IndexError for a code that matches no pixel: Transforms.mask_to_roi
+    (derender3d/datasets.py:95-103) indexes an empty array there."""
+    from sdn_hip import ops
+    _on_gpu(scene_u8, 'scene_u8')
+    if not isinstance(codes, torch.Tensor):
+        codes = torch.from_numpy(np.ascontiguousarray(np.asarray(codes).astype(np.uint8).reshape(-1, 3))).to(scene_u8.device)
+    masks, rois, areas = ops.scene_gt_masks(scene_u8, codes)
+    packed = torch.cat([rois, areas[:, None]], dim=1).cpu().numpy()
+    rois, areas = np.ascontiguousarray(packed[:, :4]), np.ascontiguousarray(packed[:, 4])
+    empty = np.where(areas == 0)[0]
+    if empty.size:
+        raise IndexError('code %d (%s) matches no pixel of the scene' % (int(empty[0]), codes[int(empty[0])].tolist()))
+    return masks, rois, areas
+
+
 # ---------------------------------------------------------------------------------------------------- edit: host half
 def match_operations(mroi_norms, operations, camera):
     """main.py:468-479: [(object index, operation index)] in the reference's iteration order.  mroi_norms: float32 [N, 2]
@@ -243,11 +263,13 @@ class SceneSession:
     image_u8   uint8 [3, H, W] CUDA;  masks float32 [N, 1, H, W] CUDA, binary;  class_ids [N], rois [N, 4] host sequences
     image_ignores  optional binary [N, 1, H, W] CUDA occlusion maps instead of the depth order (main.py:416)
     ignore_pairing 'reference' (sorted position j with roi j, main.py:419) or 'object'
+    mask_areas optional host sequence [N]: the pixel count of every mask, where the caller has it (from_detections,
+               from_scene_gt); the interest test then reads it instead of summing the planes
     Readable: rgbs, masks, ignores (the crops), blob, interests (host list of bool), image_masks."""
 
     def __init__(self, model, camera, image_u8, class_ids, masks, rois, image_ignores=None, all_interested=False,
                  mean=(0.5, 0.5, 0.5), std=(0.25, 0.25, 0.25), image_size=224, mask_size=256, ignore_pairing='reference',
-                 metas=None):
+                 metas=None, mask_areas=None):
         _on_gpu(image_u8, 'image_u8')
         _on_gpu(masks, 'masks')
         if image_u8.dtype != torch.uint8 or image_u8.dim() != 3 or image_u8.shape[0] != 3:
@@ -276,6 +298,10 @@ class SceneSession:
         # main.py:347-355; the one device-to-host copy of the construction, issued after the encoder is queued
         if all_interested:
             self.interests = [True] * n
+        elif mask_areas is not None:
+            if len(mask_areas) != n:
+                raise ValueError('%d mask areas for %d objects' % (len(mask_areas), n))
+            self.interests = [c in (1, 2) and int(a) > 16 * 16 for c, a in zip(self.class_ids, mask_areas)]
         else:
             big = (masks.sum(dim=3).sum(dim=2).reshape(-1) > 16 * 16).cpu().tolist()
             self.interests = [c in (1, 2) and bool(b) for c, b in zip(self.class_ids, big)]
@@ -285,6 +311,52 @@ class SceneSession:
                                     image_ignores=image_ignores)
         self._stacked = {}
         self.last_losses = None
+
+    # ------------------------------------------------------------------------------------------------ from the detector
+    @classmethod
+    def from_detections(cls, model, camera, image_u8, detections, mrcnn_mask, window, max_objects=16, **kwargs):
+        """The session of a frame from what the detector's heads emit (maskrcnn/model.py:1636: detections [D, 6] in the
+        molded image's pixels, mrcnn_mask float32 [D, C, Mh, Mw], both CUDA) and the molded image's `window`
+        (maskrcnn.detections.mold_window): model.py:1638-1653, 2084-2143 and main.py:797-818 without the masks leaving the
+        device.  The D x 6 table goes to the host for the box arithmetic; one sdn_unmold_masks launch counts the pixels of
+        every detection's mask (D integers to the host), the `max_objects` largest are selected as main.py:812 does, and a
+        second launch writes the planes of those only.  ValueError without a detection or for a box that leaves the frame
+        (the reference skips such a frame, main.py:809).  Readable besides SceneSession's: detection_sels (indices among the
+        surviving detections, largest first), rois, scores, mask_areas."""
+        from maskrcnn import detections as _det
+        _on_gpu(image_u8, 'image_u8')
+        _on_gpu(mrcnn_mask, 'mrcnn_mask')
+        H, W = int(image_u8.shape[1]), int(image_u8.shape[2])
+        det_host = detections.detach().cpu().numpy() if isinstance(detections, torch.Tensor) else np.asarray(detections)
+        boxes, class_ids, scores, keep = _det.unmold_boxes(det_host, (H, W), window)
+        if boxes.shape[0] < 1:
+            raise ValueError('no detections')
+        plan = _det.UnmoldPlan(mrcnn_mask, boxes, class_ids, keep, H, W)
+        areas = plan.areas().cpu().numpy()
+        sels = _det.select_largest(areas, max_objects)
+        masks, _ = plan.masks(sels)
+        self = cls(model, camera, image_u8, class_ids[sels], masks, boxes[sels], mask_areas=areas[sels], **kwargs)
+        self.detection_sels, self.rois, self.scores, self.mask_areas = sels, boxes[sels], scores[sels], areas[sels]
+        return self
+
+    @classmethod
+    def from_scene_gt(cls, model, camera, image_u8, scene_u8, codes, class_ids, metas=None, max_objects=16, **kwargs):
+        """The session of a frame from ground truth (main.py:724-761, 812-818): scene_u8 uint8 [H, W, 3] CUDA, the instance-
+        colour image; codes [K, 3] the objects' colours (host or CUDA), class_ids [K], metas optional list [K].  One
+        sdn_scene_gt_masks launch makes the K masks, rois and pixel counts (5 K integers to the host); the `max_objects`
+        largest are kept.  IndexError for a code that matches no pixel, as Transforms.mask_to_roi."""
+        masks, rois, areas = scene_gt_inputs(scene_u8, codes)
+        if len(class_ids) != rois.shape[0]:
+            raise ValueError('%d class ids for %d codes' % (len(class_ids), rois.shape[0]))
+        from maskrcnn import detections as _det
+        sels = _det.select_largest(areas, max_objects)
+        class_ids = np.asarray(class_ids)[sels]
+        metas = [metas[i] for i in sels.tolist()] if metas is not None else None
+        if len(sels) < masks.shape[0] or not np.array_equal(sels, np.arange(len(sels))):
+            masks = masks.index_select(0, torch.as_tensor(sels.copy(), dtype=torch.long).to(masks.device))
+        self = cls(model, camera, image_u8, class_ids, masks, rois[sels], metas=metas, mask_areas=areas[sels], **kwargs)
+        self.detection_sels, self.rois, self.mask_areas = sels, rois[sels], areas[sels]
+        return self
 
     # ------------------------------------------------------------------------------------------------ optimisation
     @staticmethod

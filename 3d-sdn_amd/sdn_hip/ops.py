@@ -909,3 +909,61 @@ def scene_edit(theta_deltas, translation2ds, log_depths, mroi_norms, droi_norms,
         check(lib().sdn_scene_edit(ptr(th), ptr(tr), ptr(ld), ptr(mr), ptr(dr), ptr(interests), ptr(records) if P else None, F, N,
                                    P, ptr(o_th), ptr(o_tr), ptr(o_ld), ptr(o_in), stream()))
     return o_th, o_tr, o_ld, o_in
+
+
+UNMOLD_OBJ_INTS = 12   # one row of sdn_unmold_masks's object table
+
+
+def unmold_masks(mrcnn_mask, objs_host, tables, H, W, planes=True, areas=True):
+    """Mask R-CNN's soft masks as binary full-frame planes, all objects in one launch (sdn_unmold_masks; maskrcnn/utils.py:
+    378-395 per detection on the host): bytescale, Pillow's bilinear resize to the box, >= 0.5, paste -- bit for bit.
+    mrcnn_mask [D, C, Mh, Mw] fp32 CUDA in the network's own layout; objs_host numpy int32 [n, 12] rows (detection index,
+    class id, y1, x1, y2, x2, tables of the rows, tables of the columns) and tables = (objs [n, 12], bounds, kk8) int32 CUDA
+    tensors as geometric/maskrcnn/detections.unmold_tables prepares them.  Returns (masks [n, 1, H, W] fp32 holding 0.0 / 1.0
+    or None, areas int32 [n] or None); planes=False makes only the areas.  Nothing is copied to the host."""
+    mrcnn_mask = _f32(mrcnn_mask, 'mrcnn_mask')
+    if mrcnn_mask.dim() != 4:
+        raise ValueError('mrcnn_mask must be [D, C, Mh, Mw], got %s' % (tuple(mrcnn_mask.shape),))
+    if not (planes or areas):
+        raise ValueError('neither planes nor areas asked for')
+    objs_host = np.ascontiguousarray(objs_host, dtype=np.int32)
+    if objs_host.ndim != 2 or objs_host.shape[1] != UNMOLD_OBJ_INTS or objs_host.shape[0] < 1:
+        raise ValueError('objs_host must be int32 [n, %d] with n >= 1, got %s' % (UNMOLD_OBJ_INTS, objs_host.shape))
+    n = objs_host.shape[0]
+    objs, bounds, kk8 = (want(t, torch.int32, name) for t, name in zip(tables, ('objs', 'bounds', 'kk8')))
+    if tuple(objs.shape) != (n, UNMOLD_OBJ_INTS):
+        raise ValueError('objs must be [%d, %d], got %s' % (n, UNMOLD_OBJ_INTS, tuple(objs.shape)))
+    if bounds.dim() != 2 or bounds.shape[1] != 2 or kk8.dim() != 1:
+        raise ValueError('bounds must be [M, 2] and kk8 [K], got %s, %s' % (tuple(bounds.shape), tuple(kk8.shape)))
+    D, C, Mh, Mw = mrcnn_mask.shape
+    dev = mrcnn_mask.device
+    with torch.cuda.device(dev):
+        masks = torch.empty(n, 1, H, W, device=dev) if planes else None
+        counts = torch.empty(n, dtype=torch.int32, device=dev) if areas else None
+        check(lib().sdn_unmold_masks(ptr(mrcnn_mask), D, C, Mh, Mw, objs_host.ctypes.data, ptr(objs), n, ptr(bounds), bounds.shape[0],
+                                     ptr(kk8), kk8.shape[0], H, W, ptr(masks), ptr(counts), stream()))
+    return masks, counts
+
+
+def scene_gt_masks(scene_u8, codes):
+    """--source gt (sdn_scene_gt_masks; geometric/scripts/main.py:745-746 with derender3d/datasets.py:75-76, 95-103 per object
+    on the host): scene_u8 uint8 [H, W, 3] CUDA, the instance-colour image; codes uint8 [K, 3] CUDA.  Returns (masks
+    [K, 1, H, W] fp32 = all(scene == code, axis 2), rois int32 [K, 4] = (first row, first column, last row + 1, last column
+    + 1), areas int32 [K]).  A code that matches nothing has area 0 and an invalid roi (first > last); mask_to_roi raises for
+    it, and derender3d.scene.scene_gt_inputs does.  Nothing is copied to the host."""
+    scene_u8 = want(scene_u8, torch.uint8, 'scene_u8')
+    codes = want(codes, torch.uint8, 'codes')
+    if scene_u8.dim() != 3 or scene_u8.shape[2] != 3:
+        raise ValueError('scene_u8 must be uint8 [H, W, 3], got %s' % (tuple(scene_u8.shape),))
+    if codes.dim() != 2 or codes.shape[1] != 3 or codes.shape[0] < 1:
+        raise ValueError('codes must be uint8 [K, 3] with K >= 1, got %s' % (tuple(codes.shape),))
+    if codes.device != scene_u8.device:
+        raise ValueError('codes is on %s, scene_u8 on %s' % (codes.device, scene_u8.device))
+    H, W, K = scene_u8.shape[0], scene_u8.shape[1], codes.shape[0]
+    dev = scene_u8.device
+    with torch.cuda.device(dev):
+        masks = torch.empty(K, 1, H, W, device=dev)
+        rois = torch.empty(K, 4, dtype=torch.int32, device=dev)
+        areas = torch.empty(K, dtype=torch.int32, device=dev)
+        check(lib().sdn_scene_gt_masks(ptr(scene_u8), ptr(codes), K, H, W, ptr(masks), ptr(rois), ptr(areas), stream()))
+    return masks, rois, areas

@@ -69,10 +69,10 @@ const char* sdn_last_error(void);
  * buffer changes its required size behind an unchanged signature (r04: the `key` / `acc` scratch of
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
- * sdn_scene_edit added).  A binding
+ * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6).  A binding
  * must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise
  * (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 10
+#define SDN_ABI_VERSION 11
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -515,6 +515,35 @@ int sdn_scene_edit(const float* theta_deltas, const float* translation2ds, const
                    const float* droi_norms, const uint8_t* interests, const int32_t* records, int F, int N, int P,
                    float* theta_out, float* translation_out, float* log_depth_out, uint8_t* interests_out, sdnStream stream);
 
+/* ---- the detector's output as binary full-frame masks: geometric/maskrcnn/model.py:1638-1653 (detect's tail), :2084-2143
+ * (MaskRCNN.unmold_detections), maskrcnn/utils.py:378-395 (unmold_mask) and geometric/scripts/main.py:797-818 -------------------
+ * The reference copies mrcnn_mask to the host, runs scipy.misc.imresize(.., 'bilinear') per detection, thresholds, pastes into
+ * uint8 planes, sums each plane to pick the 16 largest and uploads the survivors as float32.  sdn_unmold_masks does, for n
+ * objects in one launch and bit for bit, per object:
+ *   1. bytescale of plane (det, cls) of mrcnn_mask [D, C, Mh, Mw] (scipy 1.0.1 misc/pilutil.py under numpy 1.14: fp32 array
+ *      arithmetic): cmin / cmax over the plane, cscale = cmax - cmin (0 -> 1), scale = (float)(255.0 / (double)cscale),
+ *      byte = (uint8)(clip((x - cmin) * scale + 0, 0, 255) + 0.5) -- so the threshold below is relative to the plane's range;
+ *   2. Pillow's BILINEAR resize of the bytes to (y2 - y1, x2 - x1): horizontal pass rounded to uint8, then the vertical pass;
+ *   3. (float)v / 255 >= 0.5, i.e. v >= 128;
+ *   4. paste at [y1:y2, x1:x2].
+ * masks [n, 1, H, W] fp32 (may be NULL) receives exactly 0.0 / 1.0, every element written (no memset needed); areas [n] int32
+ * (may be NULL, not both) the number of ones (cleared by the call).  With masks NULL only the areas are made.
+ * objs: DEVICE int32 [n, 12] rows (detection index, class id, y1, x1, y2, x2, then for the rows Mh -> y2 - y1 and for the
+ * columns Mw -> x2 - x1: first row of `bounds`, first element of `kk8`, ksize -- 0 when the sizes are equal and Pillow skips
+ * the pass); objs_host: the same table on the HOST, validated before the launch (a box that is empty or leaves the frame, an
+ * index outside mrcnn_mask, a table outside the n_bounds rows of `bounds` / n_kk8 elements of `kk8` is SDN_EINVAL).  bounds /
+ * kk8 as for sdn_composite_frame.  Mh, Mw <= 64. */
+int sdn_unmold_masks(const float* mrcnn_mask, int D, int C, int Mh, int Mw, const int32_t* objs_host, const int32_t* objs, int n,
+                     const int32_t* bounds, int n_bounds, const int32_t* kk8, int n_kk8, int H, int W, float* masks,
+                     int32_t* areas, sdnStream stream);
+/* ---- the same inputs from ground truth (--source gt): geometric/scripts/main.py:724-795 with derender3d/datasets.py:75-76
+ * (Transforms.scene_to_mask) and :95-103 (mask_to_roi), which run per object on the host -----------------------------------------
+ * scene uint8 [H, W, 3], codes uint8 [K, 3] (both DEVICE) -> masks [K, 1, H, W] fp32 = all(scene == code, axis 2),
+ * rois int32 [K, 4] = (first row, first column, last row + 1, last column + 1) of each mask, areas int32 [K].  A code that
+ * matches no pixel leaves area 0 and the roi (INT_MAX, INT_MAX, 0, 0): mask_to_roi raises there, and so must the caller. */
+int sdn_scene_gt_masks(const uint8_t* scene, const uint8_t* codes, int K, int H, int W, float* masks, int32_t* rois,
+                       int32_t* areas, sdnStream stream);
+
 /* ---- PerspectiveTransform: derender3d/models/transforms.py:102-158, all objects of a frame at once -----------------------
  * out[b,v] = zoom( shear( R(quat[b]) (verts[b,v] * scales[b]) + trans[b] ) ),  shear: x -= x0/z0 * z, y -= y0/z0 * z with
  * (x0,y0,z0) = persp[b].  Test-time form (zoom_fixed NULL, :147-158): zooms[b] = min_v |z| / max(|x|,|y|) * zoom_to[b];
@@ -639,8 +668,9 @@ int sdn_timing_enable(int enable);
 int sdn_timing_read(double* ms_total, long* launches);
 /* the same for any timed kernel family: slot 0 k_raster_tiles, 1 the silhouette edge-gradient kernels, 2 the MFMA forward /
  * data-gradient kernels (k_conv_gemm, k_conv_tile, k_conv_halo, k_conv_s2), 3 the MFMA weight-gradient kernels (k_conv_wgrad,
- * k_wgrad_tile), 4 the exact-fp32 head kernels (k_conv_narrow_fwd, k_wgrad_narrow), 5 k_raster_tiles_k1; *work (may be NULL)
- * receives the summed algorithmic work of the launches (flops for the conv slots, 0 for the raster slots). */
+ * k_wgrad_tile), 4 the exact-fp32 head kernels (k_conv_narrow_fwd, k_wgrad_narrow), 5 k_raster_tiles_k1, 6 k_unmold_masks and
+ * k_scene_gt_masks; *work (may be NULL) receives the summed algorithmic work of the launches (flops for the conv slots, 0 for
+ * the raster slots, bytes of the planes for slot 6). */
 int sdn_timing_read_slot(int slot, double* ms_total, long* launches, double* work);
 /* The conv launchers compute their work from the PADDED channel counts they are handed.  A caller that knows the layer's
  * true channel counts declares the work (flops) of the next timed launch this thread issues; sdn_program_run does so for
