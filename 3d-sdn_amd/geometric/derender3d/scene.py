@@ -13,6 +13,7 @@ prepares only what is host data anyway (rois, Pillow's resampling tables, the JS
 textural/edit.py's `EditSession`: `SceneSession(...).edit(lists)` -> frames -> `EditSession(...).render_batch(frames)`.
 `SceneSession.from_detections` starts from the detector's heads (maskrcnn/detections.py, sdn_unmold_masks) and
 `SceneSession.from_scene_gt` from a ground-truth instance image (sdn_scene_gt_masks; main.py:724-761).
+`SceneSession.edit_2d` paints the 2D / 2D+ baselines of the same frame (derender3d/scene2d.py; main.py:215-322).
 
 Two quirks of the reference are kept on purpose (parity is the contract):
   * crop_square pads the right / bottom by max(0, roi end + d - size) although its window ends one pixel further when
@@ -461,6 +462,12 @@ class SceneSession:
             blob.update(self.model.render(blob))
         self.last_blob = blob
         return self._frames(blob, interests, F, paste_masks=False)
+
+    def edit_2d(self, operation_lists, use_ry=False):
+        """The 2D (use_ry: 2D+) baseline of the same frame (main.py:215-322; derender3d/scene2d.py): F operation lists -> F
+        `Frame2D`s painted from this session's cover words.  All objects are interesting there, whatever `interests` says."""
+        from derender3d import scene2d
+        return scene2d.Scene2D.from_cover(self.class_ids, self.cover, self.plan.rois).edit(operation_lists, use_ry)
 
     def reconstruct(self):
         """The reference's `operations=None`: no edit; the detector masks of non-interesting objects are pasted

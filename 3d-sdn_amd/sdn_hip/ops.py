@@ -967,3 +967,51 @@ def scene_gt_masks(scene_u8, codes):
         areas = torch.empty(K, dtype=torch.int32, device=dev)
         check(lib().sdn_scene_gt_masks(ptr(scene_u8), ptr(codes), K, H, W, ptr(masks), ptr(rois), ptr(areas), stream()))
     return masks, rois, areas
+
+
+PAINT2D_REC_INTS = 16   # one row of sdn_scene_paint2d's record table
+
+
+def scene_paint2d(cover, n, records_host=None, tables=None, frames=1):
+    """The 2D / 2D+ baselines' instance maps, F frames in one launch (sdn_scene_paint2d; geometric/scripts/main.py:293-312 per
+    object and frame on the host): every object's mask window resized by Pillow's bilinear filter and pasted, objects in index
+    order -- bit for bit.  cover: scene_cover(masks) of the n = N masks, int32 [ceil(N / 32), H, W]; records_host numpy int32 [F, N, 16] rows
+    (active, window r0, c0, h, w, output h', w', paste top, left, tables of the rows, tables of the columns, unused) and
+    tables = (records [F, N, 16], bounds [M, 2], kk8 [K]) int32 CUDA tensors as derender3d.scene2d.paint_tables prepares
+    them.  Without records ("identity") `frames` copies of the unedited masks painted in index order (main.py:236-238).
+    Returns uint8 [F, 1, H, W]: object index + 1, 0 where nothing is.  Nothing is copied to the host."""
+    cover = want(cover, torch.int32, 'cover')
+    if cover.dim() != 3:
+        raise ValueError('cover must be the int32 [ceil(N / 32), H, W] tensor of scene_cover, got %s' % (tuple(cover.shape),))
+    chunks, H, W = cover.shape
+    dev = cover.device
+    N = int(n)
+    if (N + 31) // 32 != chunks:
+        raise ValueError('cover holds %d words per pixel, %d objects need %d' % (chunks, N, (N + 31) // 32))
+    if records_host is None:
+        if tables is not None:
+            raise ValueError('scene_paint2d: tables without records_host')
+        F = int(frames)
+        with torch.cuda.device(dev):
+            out = torch.empty(F, 1, H, W, dtype=torch.uint8, device=dev)
+            check(lib().sdn_scene_paint2d(ptr(cover), None, None, F, N, None, 0, None, 0, H, W, ptr(out), stream()))
+        return out
+    records_host = np.ascontiguousarray(records_host, dtype=np.int32)
+    if records_host.ndim != 3 or records_host.shape[2] != PAINT2D_REC_INTS or records_host.shape[0] < 1 or records_host.shape[1] < 1:
+        raise ValueError('records_host must be int32 [F, N, %d] with F, N >= 1, got %s' % (PAINT2D_REC_INTS, records_host.shape))
+    F = records_host.shape[0]
+    if records_host.shape[1] != N:
+        raise ValueError('records_host holds %d objects per frame, n is %d' % (records_host.shape[1], N))
+    recs, bounds, kk8 = (want(t, torch.int32, name) for t, name in zip(tables, ('records', 'bounds', 'kk8')))
+    if tuple(recs.shape) != (F, N, PAINT2D_REC_INTS):
+        raise ValueError('records must be [%d, %d, %d], got %s' % (F, N, PAINT2D_REC_INTS, tuple(recs.shape)))
+    if bounds.dim() != 2 or bounds.shape[1] != 2 or kk8.dim() != 1:
+        raise ValueError('bounds must be [M, 2] and kk8 [K], got %s, %s' % (tuple(bounds.shape), tuple(kk8.shape)))
+    for t, name in ((recs, 'records'), (bounds, 'bounds'), (kk8, 'kk8')):
+        if t.device != dev:
+            raise ValueError('%s is on %s, cover on %s' % (name, t.device, dev))
+    with torch.cuda.device(dev):
+        out = torch.empty(F, 1, H, W, dtype=torch.uint8, device=dev)
+        check(lib().sdn_scene_paint2d(ptr(cover), records_host.ctypes.data, ptr(recs), F, N, ptr(bounds), bounds.shape[0],
+                                      ptr(kk8), kk8.shape[0], H, W, ptr(out), stream()))
+    return out

@@ -69,10 +69,10 @@ const char* sdn_last_error(void);
  * buffer changes its required size behind an unchanged signature (r04: the `key` / `acc` scratch of
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
- * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6).  A binding
+ * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added).  A binding
  * must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise
  * (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 11
+#define SDN_ABI_VERSION 12
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -543,6 +543,25 @@ int sdn_unmold_masks(const float* mrcnn_mask, int D, int C, int Mh, int Mw, cons
  * matches no pixel leaves area 0 and the roi (INT_MAX, INT_MAX, 0, 0): mask_to_roi raises there, and so must the caller. */
 int sdn_scene_gt_masks(const uint8_t* scene, const uint8_t* codes, int K, int H, int W, float* masks, int32_t* rois,
                        int32_t* areas, sdnStream stream);
+
+/* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
+ * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
+ * to (int(d0), int(d1)), pastes it into a new frame-sized 'L' image at (int(m1 - d1 / 2), int(m0 - d0 / 2)), uploads it,
+ * torch.round()s it and blends (1 - m) * map + m * (1 + index), objects in index order.  sdn_scene_paint2d paints F frames in
+ * one launch, bit for bit:
+ *   out uint8 [F, 1, H, W]: per pixel the HIGHEST active object index n whose pasted, resized mask covers it, + 1; 0 for none.
+ *   "Covers": the pixel lies inside the paste box (PIL's paste clips at the frame; a box wholly outside paints nothing) and
+ *   Pillow's resize of the 0 / 255 window evaluated there -- horizontal pass rounded and clipped to 8 bits, then the vertical
+ *   pass, 22-bit fixed point, a pass skipped when its size does not change -- is v with round(v / 255) == 1, i.e. v >= 128.
+ * cover: the words of sdn_scene_cover for the N masks [ceil(N / 32), H W].  recs: DEVICE int32 [F, N, 16] rows (active flag,
+ * window first row, first column, rows, columns, output rows, columns, paste top, left, then for the rows and for the columns:
+ * first row of `bounds`, first element of `kk8`, ksize -- 0 when the sizes are equal --, one unused int); recs_host: the same
+ * table on the HOST, validated before the launch (an active row whose window is empty or leaves the frame, whose output size
+ * is below 1, or whose tables lie outside the n_bounds rows of `bounds` / n_kk8 elements of `kk8` is SDN_EINVAL).  bounds / kk8
+ * as for sdn_composite_frame.  With recs and recs_host NULL ("identity"; bounds / kk8 unused) every frame is the unedited masks
+ * painted in index order, the highest set cover bit + 1: the NAME-ref.png map of main.py:236-238.  N <= 255 (uint8 ids). */
+int sdn_scene_paint2d(const uint32_t* cover, const int32_t* recs_host, const int32_t* recs, int F, int N, const int32_t* bounds,
+                      int n_bounds, const int32_t* kk8, int n_kk8, int H, int W, uint8_t* out, sdnStream stream);
 
 /* ---- PerspectiveTransform: derender3d/models/transforms.py:102-158, all objects of a frame at once -----------------------
  * out[b,v] = zoom( shear( R(quat[b]) (verts[b,v] * scales[b]) + trans[b] ) ),  shear: x -= x0/z0 * z, y -= y0/z0 * z with
