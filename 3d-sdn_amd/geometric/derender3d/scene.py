@@ -12,7 +12,9 @@ pre-pass sdn_scene_cover), F edit lists are one launch (sdn_scene_edit) and one 
 prepares only what is host data anyway (rois, Pillow's resampling tables, the JSON).  `SceneSession` is the counterpart of
 textural/edit.py's `EditSession`: `SceneSession(...).edit(lists)` -> frames -> `EditSession(...).render_batch(frames)`.
 `SceneSession.from_detections` starts from the detector's heads (maskrcnn/detections.py, sdn_unmold_masks) and
-`SceneSession.from_scene_gt` from a ground-truth instance image (sdn_scene_gt_masks; main.py:724-761).
+`SceneSession.from_scene_gt` from a ground-truth instance image (sdn_scene_gt_masks; main.py:724-761) and
+`SceneSession.from_cityscapes_gt` from a Cityscapes instance-id map and its disparity map (sdn_scene_id_stats,
+sdn_scene_id_planes; main.py:763-795), the one source that supplies its own ignore maps.
 `SceneSession.edit_2d` paints the 2D / 2D+ baselines of the same frame (derender3d/scene2d.py; main.py:215-322).
 
 Two quirks of the reference are kept on purpose (parity is the contract):
@@ -154,17 +156,27 @@ def nearer_words(order, pairing='reference'):
     return before
 
 
-def ignore_crops(plan, cover, log_depths=None, droi_norms=None, pairing='reference', image_ignores=None):
+def ignore_crops(plan, cover, log_depths=None, droi_norms=None, pairing='reference', image_ignores=None, ignore_cover=None):
     """main.py:405-421 for all objects -> ignores [N,1,S_m,S_m].  Either the depth order (log_depths [N,1], droi_norms [N,2]:
     sorted on the device, stable, ties keep index order) over the masks' `cover`, or caller-supplied binary image_ignores
-    [N,1,H,W] (main.py:416).  No device-to-host copy."""
+    [N,1,H,W] (main.py:416), or the same maps as cover words already (ignore_cover int32 [ceil(N / 32), H, W]: bit n = map n,
+    as ops.scene_cover(image_ignores) would make them; not both).  No device-to-host copy."""
     from sdn_hip import ops
-    if image_ignores is not None:
-        _on_gpu(image_ignores, 'image_ignores')
-        if tuple(image_ignores.shape) != (plan.n, 1, plan.height, plan.width):
-            raise ValueError('image_ignores must be [%d, 1, %d, %d], got %s'
-                             % (plan.n, plan.height, plan.width, tuple(image_ignores.shape)))
-        icover = ops.scene_cover(image_ignores)
+    if image_ignores is not None and ignore_cover is not None:
+        raise ValueError('image_ignores and ignore_cover are the same maps in two forms: pass one of them')
+    if image_ignores is not None or ignore_cover is not None:
+        if image_ignores is not None:
+            _on_gpu(image_ignores, 'image_ignores')
+            if tuple(image_ignores.shape) != (plan.n, 1, plan.height, plan.width):
+                raise ValueError('image_ignores must be [%d, 1, %d, %d], got %s'
+                                 % (plan.n, plan.height, plan.width, tuple(image_ignores.shape)))
+            icover = ops.scene_cover(image_ignores)
+        else:
+            _on_gpu(ignore_cover, 'ignore_cover')
+            if ignore_cover.dtype != torch.int32 or tuple(ignore_cover.shape) != ((plan.n + 31) // 32, plan.height, plan.width):
+                raise ValueError('ignore_cover must be int32 [%d, %d, %d], got %s %s'
+                                 % ((plan.n + 31) // 32, plan.height, plan.width, ignore_cover.dtype, tuple(ignore_cover.shape)))
+            icover = ignore_cover
         nearer = _object_bits(torch.arange(plan.n, device=icover.device))     # slot n = map n alone
     else:
         _on_gpu(log_depths, 'log_depths')
@@ -193,6 +205,69 @@ def scene_gt_inputs(scene_u8, codes):
     if empty.size:
         raise IndexError('code %d (%s) matches no pixel of the scene' % (int(empty[0]), codes[int(empty[0])].tolist()))
     return masks, rois, areas
+
+
+
+# ---------------------------------------------------------------------------------------------------- Cityscapes ground truth
+class CityscapesCamera:
+    """derender3d/datasets.py:788-791, the one camera the reference uses for every Cityscapes frame"""
+    focal = 2250.0
+    u0 = 925.0
+    v0 = 460.0
+
+
+def percentile95_threshold(n, lo, hi):
+    """floor(np.percentile(values, 95)) from the two order statistics it interpolates between, for arrays of objects: n the
+    number of values, lo / hi those of rank floor((n - 1) 0.95) and the next (sdn_scene_id_stats) -> int32 thr; 0 where n == 0
+    (main.py:778).  float64, operation for operation numpy's default `linear` method (lib/_function_base_impl.py: _lerp): the
+    rounding of lo + (hi - lo) g decides pixels where it lands on an integer.  The disparities are integers, so
+    `disparity > percentile` is `disparity > thr`."""
+    n = np.asarray(n, dtype=np.int64)
+    lo, hi = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    v = (n - 1) * np.true_divide(95, 100)
+    g = v - np.floor(v)
+    d = hi - lo
+    t = lo + d * g
+    t = np.where(g >= 0.5, hi - d * (1 - g), t)
+    t = np.where(d == 0, lo, t)
+    return np.where(n > 0, np.floor(t), 0).astype(np.int32)
+
+
+def _cityscapes_select(scene, disparity, category, max_objects):
+    """the statistics of every id of the category, ONE device-to-host copy (the table), and the host's part of main.py:766-780,
+    812: (sels, ids, rois, areas, thr) of the `max_objects` largest, largest first, numpy; sels are positions among the present
+    ids in ascending order, the rest int32"""
+    from maskrcnn import detections as _det
+    from sdn_hip import ops
+    _on_gpu(scene, 'scene')
+    _on_gpu(disparity, 'disparity')
+    table = ops.scene_id_stats(scene, disparity, category).cpu().numpy()
+    present = np.flatnonzero(table[:, 0] > 0)                     # ascending ids: np.unique's order
+    if present.size == 0:
+        raise ValueError('no object of category %d in the scene' % category)    # the reference's np.stack([]) raises
+    sels = _det.select_largest(table[present, 0].astype(np.float32), max_objects)    # float32 sums, as main.py:812 sorts them
+    rows = table[present[sels]]
+    ids = (present[sels] + 1000 * int(category)).astype(np.int32)
+    thr = percentile95_threshold(rows[:, 5], rows[:, 6], rows[:, 7])
+    return sels, ids, np.ascontiguousarray(rows[:, 1:5]), np.ascontiguousarray(rows[:, 0]), thr
+
+
+def cityscapes_gt_inputs(scene, disparity, category=26, max_objects=16):
+    """main.py:763-795, 812-818 without the maps leaving the device: scene int32 [H, W] CUDA, the instance-id map (id =
+    category * 1000 + k); disparity int32 [H, W] CUDA, a 16-bit map's values.  sdn_scene_id_stats, one device-to-host copy
+    (the table), on the host the present ids in ascending order, the `max_objects` largest masks and their thresholds, one
+    upload (ids and thr), one sdn_scene_id_planes launch.  Returns (masks float32 [n, 1, H, W] CUDA, ignore_cover int32
+    [ceil(n / 32), H, W] CUDA: bit k = disparity > percentile 95 of object k's non-zero disparities, rois, areas, ids, thr:
+    numpy int32) of the selected objects, largest first.  ValueError when the scene holds no object of the category."""
+    return _cityscapes_gt(scene, disparity, category, max_objects)[:6]
+
+
+def _cityscapes_gt(scene, disparity, category, max_objects, cover=True):
+    from sdn_hip import ops
+    sels, ids, rois, areas, thr = _cityscapes_select(scene, disparity, category, max_objects)
+    ids_d, thr_d = upload_int32([ids, thr], scene.device)
+    masks, words, _ = ops.scene_id_planes(scene, disparity, ids_d, thr_d, cover=cover)
+    return masks, words, rois, areas, ids, thr, sels
 
 
 # ---------------------------------------------------------------------------------------------------- edit: host half
@@ -263,6 +338,7 @@ class SceneSession:
     camera     anything with focal, u0, v0 (the reference's dataset.Camera)
     image_u8   uint8 [3, H, W] CUDA;  masks float32 [N, 1, H, W] CUDA, binary;  class_ids [N], rois [N, 4] host sequences
     image_ignores  optional binary [N, 1, H, W] CUDA occlusion maps instead of the depth order (main.py:416)
+    ignore_cover   the same maps as cover words, int32 [ceil(N / 32), H, W] CUDA (cityscapes_gt_inputs); not both
     ignore_pairing 'reference' (sorted position j with roi j, main.py:419) or 'object'
     mask_areas optional host sequence [N]: the pixel count of every mask, where the caller has it (from_detections,
                from_scene_gt); the interest test then reads it instead of summing the planes
@@ -270,7 +346,9 @@ class SceneSession:
 
     def __init__(self, model, camera, image_u8, class_ids, masks, rois, image_ignores=None, all_interested=False,
                  mean=(0.5, 0.5, 0.5), std=(0.25, 0.25, 0.25), image_size=224, mask_size=256, ignore_pairing='reference',
-                 metas=None, mask_areas=None):
+                 metas=None, mask_areas=None, ignore_cover=None):
+        if image_ignores is not None and ignore_cover is not None:
+            raise ValueError('image_ignores and ignore_cover are the same maps in two forms: pass one of them')
         _on_gpu(image_u8, 'image_u8')
         _on_gpu(masks, 'masks')
         if image_u8.dtype != torch.uint8 or image_u8.dim() != 3 or image_u8.shape[0] != 3:
@@ -309,7 +387,7 @@ class SceneSession:
         self._interests_dev = torch.tensor(self.interests, dtype=torch.uint8).to(dev)
         self.ignore_pairing = ignore_pairing
         self.ignores = ignore_crops(self.plan, self.cover, blob['_log_depths'], blob['_droi_norms'], ignore_pairing,
-                                    image_ignores=image_ignores)
+                                    image_ignores=image_ignores, ignore_cover=ignore_cover)
         self._stacked = {}
         self.last_losses = None
 
@@ -357,6 +435,20 @@ class SceneSession:
             masks = masks.index_select(0, torch.as_tensor(sels.copy(), dtype=torch.long).to(masks.device))
         self = cls(model, camera, image_u8, class_ids, masks, rois[sels], metas=metas, mask_areas=areas[sels], **kwargs)
         self.detection_sels, self.rois, self.mask_areas = sels, rois[sels], areas[sels]
+        return self
+
+    @classmethod
+    def from_cityscapes_gt(cls, model, camera, image_u8, scene, disparity, category=26, max_objects=16, **kwargs):
+        """The session of a frame from Cityscapes ground truth (main.py:763-795, 812-818): scene int32 [H, W] CUDA, the
+        instance-id map; disparity int32 [H, W] CUDA.  Every id of `category` (26: cars) is an object of class 1; the
+        `max_objects` largest are kept; each object's ignore map is disparity > percentile 95 of its own non-zero disparities
+        (cityscapes_gt_inputs).  camera: CityscapesCamera for the dataset's frames.  ValueError without an object.  Readable
+        besides SceneSession's: detection_sels (positions among the present ids in ascending order, largest first), rois,
+        mask_areas, instance_ids, ignore_thresholds."""
+        masks, cover, rois, areas, ids, thr, sels = _cityscapes_gt(scene, disparity, category, max_objects)
+        self = cls(model, camera, image_u8, [1] * len(ids), masks, rois, mask_areas=areas, ignore_cover=cover, **kwargs)
+        self.rois, self.mask_areas, self.instance_ids, self.ignore_thresholds = rois, areas, ids, thr
+        self.detection_sels = sels
         return self
 
     # ------------------------------------------------------------------------------------------------ optimisation

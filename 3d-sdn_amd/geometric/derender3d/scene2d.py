@@ -270,6 +270,19 @@ class Scene2D:
         self.metas = [metas[i] for i in sels.tolist()] if metas is not None else None
         return self
 
+    @classmethod
+    def from_cityscapes_gt(cls, image_u8, scene, disparity, category=26, max_objects=16):
+        """SceneSession.from_cityscapes_gt without the model and the camera (main.py:763-795, 812-818): scene, disparity int32
+        [H, W] CUDA; every id of `category` is an object of class 1, the `max_objects` largest are kept.  Masks and rois only:
+        the baselines take no ignore maps.  image_u8 may be None (the scene gives the frame size).  Readable besides Scene2D's:
+        detection_sels, mask_areas, instance_ids."""
+        masks, _, rois, areas, ids, _, sels = _scene._cityscapes_gt(scene, disparity, category, max_objects, cover=False)
+        if image_u8 is not None and tuple(image_u8.shape[-2:]) != tuple(masks.shape[-2:]):
+            raise ValueError('image_u8 is %s, the scene %s' % (tuple(image_u8.shape[-2:]), tuple(masks.shape[-2:])))
+        self = cls([1] * len(ids), masks, rois)
+        self.detection_sels, self.mask_areas, self.instance_ids = sels, areas, ids
+        return self
+
     def reference_map(self):
         """The unedited masks painted in index order (main.py:236-238, NAME-ref.png) -> uint8 [1, H, W].  No device-to-host
         copy."""

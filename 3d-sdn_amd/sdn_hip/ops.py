@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, lib, ptr, raster_bwd_workspace,
-               raster_workspace, stream, want)
+               raster_workspace, scene_id_workspace, stream, want)
 
 CAMERA_NONE, CAMERA_LOOK, CAMERA_LOOK_AT = 0, 1, 2
 
@@ -967,6 +967,67 @@ def scene_gt_masks(scene_u8, codes):
         areas = torch.empty(K, dtype=torch.int32, device=dev)
         check(lib().sdn_scene_gt_masks(ptr(scene_u8), ptr(codes), K, H, W, ptr(masks), ptr(rois), ptr(areas), stream()))
     return masks, rois, areas
+
+
+SCENE_ID_OBJS, SCENE_ID_COLS = 1000, 8   # the table of sdn_scene_id_stats: one row per id of the category
+
+
+def _id_maps(scene, disparity):
+    scene = want(scene, torch.int32, 'scene')
+    disparity = want(disparity, torch.int32, 'disparity')
+    if scene.dim() != 2 or scene.numel() < 1:
+        raise ValueError('scene must be int32 [H, W], got %s' % (tuple(scene.shape),))
+    if tuple(disparity.shape) != tuple(scene.shape):
+        raise ValueError('disparity must be int32 %s as the scene, got %s' % (tuple(scene.shape), tuple(disparity.shape)))
+    if disparity.device != scene.device:
+        raise ValueError('disparity is on %s, scene on %s' % (disparity.device, scene.device))
+    return scene, disparity
+
+
+def scene_id_stats(scene, disparity, category=26):
+    """--dataset cityscapes --source gt, the statistics (sdn_scene_id_stats; geometric/scripts/main.py:766-780 with
+    derender3d/datasets.py:95-103 per object on the host): scene int32 [H, W] CUDA, the instance-id map (id = category * 1000 +
+    k); disparity int32 [H, W] CUDA with values in 0 .. 65535 (verified only with SDN_DEBUG_CHECKS=1 in the environment, which
+    makes the call synchronous).  Returns the table int32 [1000, 8], row j = id - 1000 category: (area, y0, x0, y1, x1, n, lo,
+    hi) -- pixel count, roi as mask_to_roi, the number of non-zero disparities under the mask and their order statistics of
+    rank floor((n - 1) 0.95) and the next (0, 0 when n == 0): what np.percentile(., 95) interpolates between.  An absent id has
+    area 0 and an invalid roi.  Nothing is copied to the host."""
+    scene, disparity = _id_maps(scene, disparity)
+    H, W = scene.shape
+    dev = scene.device
+    with torch.cuda.device(dev):
+        table = torch.empty(SCENE_ID_OBJS, SCENE_ID_COLS, dtype=torch.int32, device=dev)
+        workspace = scene_id_workspace(dev)
+        check(lib().sdn_scene_id_stats(ptr(scene), ptr(disparity), int(category), H, W, ptr(table), ptr(workspace), stream()))
+    return table
+
+
+def scene_id_planes(scene, disparity, ids, thr, planes=True, ignore_planes=False, cover=True):
+    """The scene inputs of n selected ids in one launch (sdn_scene_id_planes; main.py:770-786): scene, disparity int32 [H, W]
+    CUDA; ids int32 [n] CUDA, the full instance ids; thr int32 [n] CUDA, floor(np.percentile(.., 95)) of each object
+    (derender3d.scene.percentile95_threshold).  Returns (masks fp32 [n, 1, H, W] = scene == ids[k] or None, ignore_cover: uint32
+    words as an int32 tensor [ceil(n / 32), H, W] in the layout of scene_cover, bit k set where disparity > thr[k], or None,
+    ignores fp32 [n, 1, H, W] of the same predicate or None).  planes / cover: not both False.  Nothing is copied to the host."""
+    scene, disparity = _id_maps(scene, disparity)
+    ids = want(ids, torch.int32, 'ids')
+    thr = want(thr, torch.int32, 'thr')
+    if ids.dim() != 1 or ids.shape[0] < 1 or tuple(thr.shape) != tuple(ids.shape):
+        raise ValueError('ids and thr must be int32 [n] with n >= 1, got %s and %s' % (tuple(ids.shape), tuple(thr.shape)))
+    if not (planes or cover):
+        raise ValueError('neither planes nor cover asked for')
+    dev = scene.device
+    for t, name in ((ids, 'ids'), (thr, 'thr')):
+        if t.device != dev:
+            raise ValueError('%s is on %s, scene on %s' % (name, t.device, dev))
+    H, W = scene.shape
+    n = ids.shape[0]
+    with torch.cuda.device(dev):
+        masks = torch.empty(n, 1, H, W, device=dev) if planes else None
+        words = torch.empty((n + 31) // 32, H, W, dtype=torch.int32, device=dev) if cover else None
+        ignores = torch.empty(n, 1, H, W, device=dev) if ignore_planes else None
+        check(lib().sdn_scene_id_planes(ptr(scene), ptr(disparity), ptr(ids), ptr(thr), n, H, W, ptr(masks), ptr(words), ptr(ignores),
+                                        stream()))
+    return masks, words, ignores
 
 
 PAINT2D_REC_INTS = 16   # one row of sdn_scene_paint2d's record table

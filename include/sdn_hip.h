@@ -69,10 +69,10 @@ const char* sdn_last_error(void);
  * buffer changes its required size behind an unchanged signature (r04: the `key` / `acc` scratch of
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
- * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added).  A binding
- * must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise
- * (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 12
+ * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
+ * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added).  A binding must compare sdn_version() with
+ * the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
+#define SDN_ABI_VERSION 13
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -543,6 +543,36 @@ int sdn_unmold_masks(const float* mrcnn_mask, int D, int C, int Mh, int Mw, cons
  * matches no pixel leaves area 0 and the roi (INT_MAX, INT_MAX, 0, 0): mask_to_roi raises there, and so must the caller. */
 int sdn_scene_gt_masks(const uint8_t* scene, const uint8_t* codes, int K, int H, int W, float* masks, int32_t* rois,
                        int32_t* areas, sdnStream stream);
+
+/* ---- the same inputs from Cityscapes ground truth (--dataset cityscapes --source gt): geometric/scripts/main.py:763-795, 812-818
+ * and the same statements in derender3d/datasets.py:930-971, with Transforms.mask_to_roi (datasets.py:95-103) ------------------
+ * The reference runs np.unique over the instance-id map (id = category * 1000 + k), keeps the ids with id // 1000 == 26 and, per
+ * object on the host, gathers the disparities under the mask, drops the zeros, takes np.percentile(., 95) of the rest (0 if
+ * nothing is left) and compares the whole disparity frame with it: the object's ignore map.
+ *
+ * sdn_scene_id_stats: scene, disparity DEVICE int32 [H, W]; the disparities lie in 0 .. 65535 (16-bit PNGs; checked only when
+ * the environment holds SDN_DEBUG_CHECKS=1, which makes the call synchronous; SDN_EINVAL otherwise).  table: DEVICE int32
+ * [1000, 8], row j = id - 1000 category: (area, y0, x0, y1, x1, n, lo, hi) -- the pixel count and the roi of mask_to_roi (first
+ * row, first column, last row + 1, last column + 1); n = the pixels under the mask whose disparity is not 0; lo, hi = those n
+ * values' order statistics of rank i = (19 (n - 1)) / 20 (= floor((n - 1) 0.95)) and min(i + 1, n - 1), zero-based, ascending,
+ * both 0 when n == 0: the two values np.percentile's `linear` method interpolates between.  The row of an absent id holds
+ * area 0 and the invalid roi (INT_MAX, INT_MAX, 0, 0) of sdn_scene_gt_masks.  An id equal to the bare category is not
+ * category * 1000 + k and is ignored (26 // 1000 == 0 in the reference).  An exact two-level radix select, five launches on
+ * `stream`, integer atomics only (the result does not depend on scheduling), nothing copied to the host.  workspace: DEVICE,
+ * sdn_scene_id_workspace_bytes (3 088 000: histograms of the high byte [1000, 256], select records [1000, 4], histograms of
+ * the low byte [1000, 2, 256], int32), aligned to 16 bytes; the call clears it and the table.
+ *
+ * sdn_scene_id_planes: the outputs of n selected objects in one launch.  ids, thr: DEVICE int32 [n], the full instance ids and
+ * the thresholds floor(np.percentile(.., 95)) (the disparities are integers: d > t is d > floor(t)), computed on the HOST from
+ * (n, lo, hi) in float64 as numpy does (derender3d.scene.percentile95_threshold).  masks [n, 1, H, W] fp32 (may be NULL): 1.0
+ * where scene == ids[k], else 0.0.  ignore_cover uint32 [ceil(n / 32), H W] (may be NULL, not both): bit (k & 31) of word
+ * k / 32 is set where disparity > thr[k] -- the layout of sdn_scene_cover.  ignores [n, 1, H, W] fp32 (may be NULL): the same
+ * predicate as planes (the reference's image_ignores).  Every element is written (no memset needed), one writer per word. */
+int sdn_scene_id_workspace_bytes(size_t* out);
+int sdn_scene_id_stats(const int32_t* scene, const int32_t* disparity, int category, int H, int W, int32_t* table,
+                       void* workspace, sdnStream stream);
+int sdn_scene_id_planes(const int32_t* scene, const int32_t* disparity, const int32_t* ids, const int32_t* thr, int n, int H, int W,
+                        float* masks, uint32_t* ignore_cover, float* ignores, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
