@@ -18,7 +18,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', 'lib', 'libsdn_hip.so'))
 RGB, ALPHA, DEPTH, AA, FACE_COLOR, SAVE_MAPS, ACCUMULATE, SERIAL_EDGES, STREAM_FACES, COUNT_WORK = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 K1_COVERAGE = 4096   # SDN_K1_COVERAGE: the reference's default ("unsafe") forward kernel's coverage rule, deterministic ties
 
-ABI_VERSION = 13   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
+ABI_VERSION = 14   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
 
 _lib = None
 _lock = threading.Lock()
@@ -105,6 +105,8 @@ def _declare(L):
     sig['sdn_scene_id_workspace_bytes'] = [ctypes.POINTER(_sz)]
     sig['sdn_scene_id_stats'] = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp]
     sig['sdn_scene_id_planes'] = [_vp, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
+    sig['sdn_assemble_planes'] = [_vp] * 5 + [_ci, _vp, _vp, _ci, _vp] + [_ci] * 9 + [_cf, _cf, _ci, _cf, _vp, _vp]
+    sig['sdn_assemble_maps'] = [_vp] * 10 + [_ci] * 9 + [_vp] * 4 + [_ci, _ci] + [_vp] * 4
     sig['sdn_perspective_transform_scratch'] = [_ci, _ci, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
     sig['sdn_perspective_transform'] = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
     sig['sdn_perspective_transform_bwd'] = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -176,7 +178,7 @@ def exported_symbols():
             'sdn_conv_tile', 'sdn_conv_wgrad_tile', 'sdn_conv_halo', 'sdn_conv_halo_blocks', 'sdn_segment_mean', 'sdn_l1_loss_fwd', 'sdn_l1_loss_bwd', 'sdn_silhouette_loss_fwd', 'sdn_silhouette_loss_bwd', 'sdn_assemble_nhwc', 'sdn_pose_params', 'sdn_pose_algebra', 'sdn_pose_algebra_bwd',
             'sdn_pose_params_bwd', 'sdn_composite_frame', 'sdn_edit_assemble', 'sdn_scene_cover', 'sdn_scene_crops', 'sdn_scene_edit',
             'sdn_unmold_masks', 'sdn_scene_gt_masks', 'sdn_scene_paint2d',
-            'sdn_scene_id_workspace_bytes', 'sdn_scene_id_stats', 'sdn_scene_id_planes',
+            'sdn_scene_id_workspace_bytes', 'sdn_scene_id_stats', 'sdn_scene_id_planes', 'sdn_assemble_planes', 'sdn_assemble_maps',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',

@@ -1076,3 +1076,125 @@ def scene_paint2d(cover, n, records_host=None, tables=None, frames=1):
         check(lib().sdn_scene_paint2d(ptr(cover), records_host.ctypes.data, ptr(recs), F, N, ptr(bounds), bounds.shape[0],
                                       ptr(kk8), kk8.shape[0], H, W, ptr(out), stream()))
     return out
+
+
+ASSEMBLE_INST_NONE, ASSEMBLE_INST_TABLE, ASSEMBLE_INST_FILL, ASSEMBLE_INST_INT = 0, 1, 2, 3   # `inst_mode` of sdn_assemble_maps
+
+
+def _assemble_items(items_host, items, name):
+    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
+    if items_host.ndim != 2 or items_host.shape[1] != 4 or items_host.shape[0] < 1:
+        raise ValueError('%s: items_host must be int32 [B, 4] with B >= 1, got %s' % (name, items_host.shape))
+    items = want(items, torch.int32, 'items')
+    if tuple(items.shape) != items_host.shape:
+        raise ValueError('%s: items must be int32 %s as items_host, got %s' % (name, items_host.shape, tuple(items.shape)))
+    return items_host, items
+
+
+def _assemble_on(dev, name, tensors):
+    for t, n in tensors:
+        if t is not None and t.device != dev:
+            raise ValueError('%s: %s is on %s, items on %s' % (name, n, t.device, dev))
+
+
+def assemble_planes(src, items_host, items, xtab, ytab, lut, C, H, W, sh, sw, h, w, normalize=True, mean=0.5, std=0.5, add=None):
+    """get_transform(opt, params)(image) for B items x C uint8 planes in one launch (sdn_assemble_planes; textural/data/
+    base_dataset.py:41-66 per item with PIL on the host): Pillow's resize [H, W] -> [sh, sw] evaluated only inside each item's crop
+    window [h, w], flip, ToTensor, Normalize, + add -- bit for bit.  src int64 [B] CUDA: the address of each item's uint8
+    [C, H, W] map, 0 for an absent map (planes of 0.0); items_host numpy int32 [B, 4] rows (crop x1, y1, flip, unused) and
+    items, the same on the device; xtab = (xmin int32 [sw], xk int32 [sw, taps]) or None exactly when sw == W, ytab likewise
+    for the rows; lut fp32 [256] (ToTensor).  The caller keeps the maps alive.  Returns fp32 [B, C, h, w].  Nothing is copied
+    to the host."""
+    items_host, items = _assemble_items(items_host, items, 'assemble_planes')
+    B = items_host.shape[0]
+    src = want(src, torch.int64, 'src')
+    lut = _f32(lut, 'lut')
+    if tuple(src.shape) != (B,) or tuple(lut.shape) != (256,):
+        raise ValueError('assemble_planes: src must be int64 [%d] and lut fp32 [256], got %s and %s'
+                         % (B, tuple(src.shape), tuple(lut.shape)))
+    tabs = []
+    for tab, n, axis in ((xtab, sw, 'x'), (ytab, sh, 'y')):
+        if tab is None:
+            tabs.append((None, None, 0))
+            continue
+        lo, k = want(tab[0], torch.int32, axis + 'min'), want(tab[1], torch.int32, axis + 'k')
+        if tuple(lo.shape) != (n,) or k.dim() != 2 or k.shape[0] != n or k.shape[1] < 1:
+            raise ValueError('assemble_planes: %smin must be int32 [%d] and %sk [%d, taps], got %s and %s'
+                             % (axis, n, axis, n, tuple(lo.shape), tuple(k.shape)))
+        tabs.append((lo, k, k.shape[1]))
+    dev = items.device
+    _assemble_on(dev, 'assemble_planes', [(src, 'src'), (lut, 'lut')] + [(t, 'a table') for tab in tabs for t in tab[:2]])
+    with torch.cuda.device(dev):
+        out = torch.empty(B, C, h, w, dtype=torch.float32, device=dev)
+        check(lib().sdn_assemble_planes(ptr(src), items_host.ctypes.data, ptr(items), ptr(tabs[0][0]), ptr(tabs[0][1]), tabs[0][2],
+                                        ptr(tabs[1][0]), ptr(tabs[1][1]), tabs[1][2], ptr(lut), B, C, H, W, sh, sw, h, w,
+                                        int(bool(normalize)), float(mean), float(std), int(add is not None),
+                                        float(add) if add is not None else 0.0, ptr(out), stream()))
+    return out
+
+
+def assemble_maps(segm, inst, pose, items_host, items, nx, ny, tabs, inst_mode, H, W, sh, sw, h, w, wrap16=False, pose_has=None,
+                  pose_val=None, min_area=1, inst_nx=None, inst_ny=None):
+    """The label, instance and pose maps of B items in two launches (sdn_assemble_maps; textural/data/vkitti_dataset.py:52-57,
+    68-118 and cityscapes_dataset.py:41-42, 55-93, 102-105 per item on the host).  segm, inst, pose: int64 [B] CUDA address
+    tables of the items' uint8 [H, W] maps (inst: int32 [H, W] maps for ASSEMBLE_INST_INT; an entry 0 = the map is absent: inst
+    is the label, or 0 for ASSEMBLE_INST_INT, whose output is an integer tensor; inst None for ASSEMBLE_INST_NONE, pose None
+    without the pose feature); items_host / items as for assemble_planes; nx int32 [sw], ny int32 [sh] NEAREST source indices,
+    None exactly where the size does not change (inst_nx, inst_ny: other indices for the instance map of ASSEMBLE_INST_INT,
+    each only where that size changes, see include/sdn_hip.h); tabs fp32 [4, 256] (label, label at an instance value of 0,
+    fill of such an instance, instance value).  pose_has int32 [B, 256], pose_val int32 [B, 256] (bins) or fp32 [B, 256, 2]
+    (cos, sin) by raw id; an id is painted where its transformed pixel count is >= min_area.  Returns (label fp32 [B,1,h,w],
+    inst fp32 -- for ASSEMBLE_INST_INT int32, or int16 with wrap16 -- [B,1,h,w] or None, pose int32 [B,1,h,w] / fp32 [B,2,h,w]
+    or None, missing int32 [B]: pixels of painted-size ids without a record).  Nothing is copied to the host."""
+    items_host, items = _assemble_items(items_host, items, 'assemble_maps')
+    B = items_host.shape[0]
+    segm = want(segm, torch.int64, 'segm')
+    inst = want(inst, torch.int64, 'inst')
+    pose = want(pose, torch.int64, 'pose')
+    nx = want(nx, torch.int32, 'nx')
+    ny = want(ny, torch.int32, 'ny')
+    inst_nx = want(inst_nx, torch.int32, 'inst_nx')
+    inst_ny = want(inst_ny, torch.int32, 'inst_ny')
+    tabs = _f32(tabs, 'tabs')
+    for t, name in ((segm, 'segm'), (inst, 'inst'), (pose, 'pose')):
+        if t is not None and tuple(t.shape) != (B,):
+            raise ValueError('assemble_maps: %s must be int64 [%d], got %s' % (name, B, tuple(t.shape)))
+    if tuple(tabs.shape) != (4, 256):
+        raise ValueError('assemble_maps: tabs must be fp32 [4, 256], got %s' % (tuple(tabs.shape),))
+    for t, n, name in ((nx, sw, 'nx'), (ny, sh, 'ny'), (inst_nx, sw, 'inst_nx'), (inst_ny, sh, 'inst_ny')):
+        if t is not None and tuple(t.shape) != (n,):
+            raise ValueError('assemble_maps: %s must be int32 [%d], got %s' % (name, n, tuple(t.shape)))
+    if inst_mode not in (ASSEMBLE_INST_NONE, ASSEMBLE_INST_TABLE, ASSEMBLE_INST_FILL, ASSEMBLE_INST_INT):
+        raise ValueError('assemble_maps: inst_mode %r' % (inst_mode,))
+    if (inst_mode != ASSEMBLE_INST_NONE) != (inst is not None):
+        raise ValueError('assemble_maps: an instance address table exactly when inst_mode is not ASSEMBLE_INST_NONE')
+    ch = 0
+    if pose is not None:
+        pose_has = want(pose_has, torch.int32, 'pose_has')
+        if pose_val is None or pose_has is None or pose_val.dtype not in (torch.int32, torch.float32):
+            raise ValueError('assemble_maps: the pose plane needs pose_has int32 and pose_val int32 or fp32')
+        pose_val = want(pose_val, pose_val.dtype, 'pose_val')
+        ch = 1 if pose_val.dtype == torch.int32 else 2
+        if tuple(pose_has.shape) != (B, 256) or tuple(pose_val.shape) != ((B, 256) if ch == 1 else (B, 256, 2)):
+            raise ValueError('assemble_maps: pose_has must be [%d, 256] and pose_val int32 [%d, 256] or fp32 [%d, 256, 2], got %s, %s'
+                             % (B, B, B, tuple(pose_has.shape), tuple(pose_val.shape)))
+    dev = items.device
+    _assemble_on(dev, 'assemble_maps', [(segm, 'segm'), (inst, 'inst'), (pose, 'pose'), (nx, 'nx'), (ny, 'ny'), (inst_nx, 'inst_nx'),
+                                        (inst_ny, 'inst_ny'), (tabs, 'tabs'), (pose_has, 'pose_has'),
+                                        (pose_val if pose is not None else None, 'pose_val')])
+    with torch.cuda.device(dev):
+        label = torch.empty(B, 1, h, w, dtype=torch.float32, device=dev)
+        inst_out = None
+        if inst_mode != ASSEMBLE_INST_NONE:
+            kind = torch.float32 if inst_mode != ASSEMBLE_INST_INT else (torch.int16 if wrap16 else torch.int32)
+            inst_out = torch.empty(B, 1, h, w, dtype=kind, device=dev)
+        pose_out = counts = None
+        if ch:
+            pose_out = torch.empty(B, ch, h, w, dtype=torch.int32 if ch == 1 else torch.float32, device=dev)
+            counts = torch.empty(B, 256, dtype=torch.int32, device=dev)
+        missing = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib().sdn_assemble_maps(ptr(segm), ptr(inst), ptr(pose), items_host.ctypes.data, ptr(items), ptr(nx), ptr(ny),
+                                      ptr(inst_nx), ptr(inst_ny), ptr(tabs), int(inst_mode), int(bool(wrap16)), B, H, W, sh, sw, h, w,
+                                      ptr(label), ptr(inst_out), ptr(pose_has) if ch else None, ptr(pose_val) if ch else None,
+                                      ch if ch else 1, int(min_area), ptr(pose_out), ptr(counts), ptr(missing), stream()))
+    return label, inst_out, pose_out, missing

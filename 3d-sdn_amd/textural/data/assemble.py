@@ -377,3 +377,243 @@ def assemble_edit(opt, params, base_item, edit_inst_u8, edit_json, codes, normal
             nrm.append(zero)
     return {'label': label, 'inst': inst, 'pose': pose, 'feat': feat, 'missing': missing, 'normal': torch.stack(nrm),
             'obj_label': obj_label, 'obj_pose': obj_pose}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the loader's item as kernels, batched (csrc/assemble.hip): vkitti_dataset.py:44-129 and cityscapes_dataset.py:32-111
+# data/cityscapes_labels.py restated as data: CITYSCAPES_LABEL_TABLE[id] = trainId + 1, 0 for the void classes (trainId 255),
+# for the label ids 0..33 (cityscapes_dataset.py:102-105; the 'license plate' row has id -1 and matches no pixel)
+CITYSCAPES_LABEL_TABLE = [0, 0, 0, 0, 0, 0, 0, 1, 2, 0, 0, 3, 4, 5, 0, 0, 0, 6, 0, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 0, 0, 17,
+                          18, 19]
+MIN_POSE_AREA = {'vkitti': 1, 'cityscapes': 256}   # cityscapes_dataset.py:82: smaller instances get no pose
+
+
+@functools.lru_cache(maxsize=64)
+def _nearest_table_generic(in_size, out_size):
+    """Pillow's NEAREST for the image modes ImagingScaleAffine does not serve (mode 'I;16': ImagingGenericTransform with
+    affine_transform): the source index of output x is (int)(a (x + 0.5)), evaluated per pixel -- not the running sum of
+    _nearest_table, which lands one lower where a (x + 0.5) is an integer the sum falls short of (128 -> 96, x = 4).  Pillow
+    takes that path whenever it resizes such an image at all; on an axis that keeps its size the index is x itself."""
+    a = np.float64(in_size) / out_size
+    idx = (a * (np.arange(out_size, dtype=np.float64) + 0.5) + 0.0).astype(np.int64)
+    return torch.from_numpy(np.minimum(idx, in_size - 1))
+
+
+def batch_geometry(opt, H, W):
+    """(sh, sw, h, w, crops) of get_transform for an [H, W] source: the size after the mode's one resize (Scale, __scale_width
+    or __make_power_2), the output size, and whether __crop applies (base_dataset.py:41-98)."""
+    roc = opt.resize_or_crop
+    sh, sw = load_size_after_scaling(opt, H, W)
+    if roc == 'none':
+        base = float(2 ** opt.n_downsample_global)
+        if opt.netG == 'local':
+            base *= (2 ** opt.n_local_enhancers)
+        sh, sw = int(round(H / base) * base), int(round(W / base) * base)
+    if 'crop' in roc and (sw > opt.fineWidth or sh > opt.fineHeight):
+        return sh, sw, opt.fineHeight, opt.fineWidth, True
+    return sh, sw, sh, sw, False
+
+
+def _label_tables(opt, dataset, inst_int):
+    """(tabs fp32 [4, 256], inst_mode): every per-value statement of the two loaders evaluated on the HOST with the loader's
+    own torch operations, for all 256 byte values -- rows: the label of a segm byte, the label where the instance value is 0,
+    the value that fills such an instance, the instance value of an inst byte (sdn_assemble_maps)."""
+    from sdn_hip import ops as _ops
+    lut = _to_tensor_lut()
+    A = lut * 255.0
+    inst = lut.clone()
+    mode = _ops.ASSEMBLE_INST_TABLE
+    if opt.inst_precomputed_path:
+        inst = inst * 255.0
+        inst = inst * 1000
+        mode = _ops.ASSEMBLE_INST_FILL
+    if dataset == 'vkitti':
+        if opt.segm_precomputed_path:
+            A = A + 1
+        A0 = A.clone()
+        if opt.inst_precomputed_path and opt.segm_precomputed_path:   # vkitti_dataset.py:75-78
+            A0[A == 2] = 5
+            A0[A == 12] = 5
+        rows = (A, A0, A0, inst)
+    else:
+        post = A.clone()
+        if not opt.segm_precomputed_path:                             # cityscapes_dataset.py:102-105
+            for i, v in enumerate(CITYSCAPES_LABEL_TABLE):
+                post[A == i] = v
+        rows = (post, post, A, inst)                                  # :63 fills from the label BEFORE the mapping
+    if opt.no_instance:
+        mode = _ops.ASSEMBLE_INST_NONE
+    elif inst_int:
+        mode = _ops.ASSEMBLE_INST_INT
+    return torch.stack(rows).numpy().astype(np.float32), mode
+
+
+def _pose_tables(opt, dataset, pose_jsons):
+    """(has int32 [B, 256], val int32 [B, 256] | fp32 [B, 256, 2]) by raw pose id p: the record the loader looks up for the
+    map value float32(p / 255) * 255 -- cityscapes: d[str(int(value))] (:84); vkitti: the record whose int(key) equals the
+    value (assemble_item) -- and np.digitize(alpha / pi, bins), or (cos, sin) of the host's libm rounded to fp32."""
+    nb = opt.feat_pose_num_bins
+    B = len(pose_jsons)
+    value = (_to_tensor_lut() * 255.0).numpy()
+    has = np.zeros((B, 256), dtype=np.int32)
+    val = np.zeros((B, 256), dtype=np.int32) if nb else np.zeros((B, 256, 2), dtype=np.float32)
+    bins = pose_bins(nb) if nb else None
+    for b, js in enumerate(pose_jsons):
+        if js is None:
+            continue
+        recs = {}
+        if dataset == 'vkitti':
+            for key, rec in js.items():
+                recs[float(int(key))] = rec
+        for p in range(1, 256):
+            rec = recs.get(float(value[p])) if dataset == 'vkitti' else js.get(str(int(value[p])))
+            if rec is None:
+                continue
+            alpha = rec['alpha']
+            has[b, p] = 1
+            if nb:
+                val[b, p] = int(np.digitize(alpha / pi, bins))
+            else:
+                val[b, p] = (cos(alpha), sin(alpha))
+    return has, val
+
+
+def _upload(dev, parts):
+    """the host arrays `parts` {name: numpy int32 / fp32 / int64 array} as ONE host-to-device copy: a dict of device views."""
+    off, total = {}, 0
+    for k, a in parts.items():
+        off[k] = total
+        total += (a.nbytes // 4 + 3) // 4 * 4   # 16-byte sections: the int64 address tables stay aligned
+    blob = np.zeros(total, dtype=np.int32)
+    for k, a in parts.items():
+        blob[off[k]:off[k] + a.nbytes // 4] = np.ascontiguousarray(a).reshape(-1).view(np.int32)
+    d = torch.from_numpy(blob).to(dev)
+    kinds = {np.dtype(np.int32): torch.int32, np.dtype(np.float32): torch.float32, np.dtype(np.int64): torch.int64}
+    return {k: d[off[k]:off[k] + a.nbytes // 4].view(kinds[a.dtype]).view(a.shape) for k, a in parts.items()}
+
+
+def assemble_batch(opt, params_list, frames, dataset='vkitti', inst_wrap_int16=False):
+    """B items of the reference's loader in four kernel launches (csrc/assemble.hip), computing only each item's crop window:
+    dataset='vkitti' is vkitti_dataset.__getitem__ (:44-129, bit-equal to assemble_item), dataset='cityscapes' is
+    cityscapes_dataset.__getitem__ (:32-111).
+      params_list  B dicts {'crop_pos': (x, y), 'flip': bool} (get_params)
+      frames       B dicts of decoded maps on ONE GPU, all of one source size: 'segm' uint8 [1, H, W], 'image' uint8 [3, H, W],
+                   'inst' uint8 [1, H, W] -- or, for the Cityscapes ground-truth instance ids, an integer [1, H, W] tensor of a
+                   wider type, handed through unscaled --, 'pose_inst' uint8 [1, H, W] with 'pose_json' (the geometric branch's
+                   NNNNN.png / .json), 'normal' uint8 [3, H, W].  inst / pose_inst / pose_json / normal absent or None: the
+                   loader's FileNotFoundError branch of that item.
+      inst_wrap_int16  the 16-bit instance map is a mode 'I;16' image: torchvision 0.2.x's ToTensor reads it through np.int16
+                   (Cityscapes ids reach 33 999 and come out negative; the result is int16) and Pillow resizes it with its
+                   generic transform (_nearest_table_generic).  PIL versions that open the PNG as mode 'I' give int32.
+    Returns {'label', 'inst' [B,1,h,w], 'image', 'normal' [B,3,h,w], 'pose' [B,1,h,w] int32 | [B,2,h,w] fp32, 'missing' int32
+    [B]} (0 where the loader leaves its default): 'missing' counts the pixels of pose ids that are large enough to be painted
+    but have no record in the JSON -- the reference raises KeyError there; they are painted 0.  The tables and the per-item
+    parameters go to the device in one copy; nothing is read back.  `--feat_depth` stays with depth_feature."""
+    from sdn_hip import ops as _ops
+    if dataset not in MIN_POSE_AREA:
+        raise ValueError('assemble_batch: dataset must be vkitti or cityscapes, got %r' % (dataset,))
+    B = len(frames)
+    if B < 1 or len(params_list) != B:
+        raise ValueError('assemble_batch: %d frames, %d params' % (B, len(params_list)))
+    if opt.label_nc == 0:
+        raise NotImplementedError('assemble_batch: label_nc == 0 (the label map as an RGB image) is assemble_item\'s')
+    maps = {k: [f.get(k) for f in frames] for k in ('segm', 'image', 'inst', 'pose_inst', 'normal')}
+    jsons = [f.get('pose_json') for f in frames]
+    planes = {'segm': 1, 'image': 3, 'inst': 1, 'pose_inst': 1, 'normal': 3}
+    shape = None
+    dev = None
+    for k, ts in maps.items():
+        for b, t in enumerate(ts):
+            if t is None:
+                if k in ('segm', 'image'):
+                    raise ValueError('assemble_batch: frame %d has no %s' % (b, k))
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError('assemble_batch expects torch tensors, frame %d %s is %r' % (b, k, type(t)))
+            if not t.is_cuda:   # as every op of this project: no host path
+                raise NotImplementedError('assemble_batch: frame %d %s is on %s; the batched assembly only runs on the GPU'
+                                          % (b, k, t.device))
+            if t.dim() != 3 or t.shape[0] != planes[k]:
+                raise ValueError('assemble_batch: frame %d %s must be [%d, H, W], got %s' % (b, k, planes[k], tuple(t.shape)))
+            if shape is None:
+                shape, dev = tuple(t.shape[1:]), t.device
+            if tuple(t.shape[1:]) != shape:
+                raise ValueError('assemble_batch: frame %d %s is %s, the call\'s source size is %s'
+                                 % (b, k, tuple(t.shape[1:]), shape))
+            if t.device != dev:
+                raise ValueError('assemble_batch: frame %d %s is on %s, the call on %s' % (b, k, t.device, dev))
+            if t.dtype != torch.uint8 and (k != 'inst' or t.dtype.is_floating_point or t.dtype == torch.bool):
+                raise TypeError('assemble_batch: frame %d %s must be uint8, got %s' % (b, k, t.dtype))
+    H, W = shape
+    use_inst = not opt.no_instance
+    wide = [t is not None and t.dtype != torch.uint8 for t in maps['inst']] if use_inst else [False] * B
+    if any(wide):
+        if opt.inst_precomputed_path:
+            raise TypeError('assemble_batch: a precomputed instance map is uint8')
+        if not all(wide):
+            raise ValueError('assemble_batch: integer and uint8 (or missing) instance maps in one call give tensors of '
+                             'different types; assemble them in separate calls')
+    sh, sw, h, w, crops = batch_geometry(opt, H, W)
+    items = np.zeros((B, 4), dtype=np.int32)
+    for b, p in enumerate(params_list):
+        if crops:
+            items[b, 0], items[b, 1] = int(p['crop_pos'][0]), int(p['crop_pos'][1])
+        items[b, 2] = 1 if (opt.isTrain and not opt.no_flip and p['flip']) else 0
+    if (items[:, :2] < 0).any():
+        raise ValueError('assemble_batch: negative crop position')
+
+    keep = []   # contiguous copies live until the launches are queued
+
+    def addresses(ts, dtype=torch.uint8):
+        a = np.zeros(B, dtype=np.int64)
+        for b, t in enumerate(ts):
+            if t is not None:
+                t = t.to(dtype).contiguous()
+                keep.append(t)
+                a[b] = t.data_ptr()
+        return a
+
+    tabs, inst_mode = _label_tables(opt, dataset, any(wide))
+    parts = {'items': items, 'lut': _to_tensor_lut().numpy(), 'tabs': tabs, 'segm': addresses(maps['segm']),
+             'image': addresses(maps['image'])}
+    if sw != W:
+        idx, k8 = _resample_table(W, sw, 'bicubic')
+        parts['xmin'], parts['xk'] = idx[:, 0].numpy().astype(np.int32), k8.numpy().astype(np.int32)
+        parts['nx'] = _nearest_table(W, sw).numpy().astype(np.int32)
+    if sh != H:
+        idx, k8 = _resample_table(H, sh, 'bicubic')
+        parts['ymin'], parts['yk'] = idx[:, 0].numpy().astype(np.int32), k8.numpy().astype(np.int32)
+        parts['ny'] = _nearest_table(H, sh).numpy().astype(np.int32)
+    if any(wide) and inst_wrap_int16:   # a mode 'I;16' map: the generic transform's indices on every axis that changes
+        if sw != W:
+            parts['inst_nx'] = _nearest_table_generic(W, sw).numpy().astype(np.int32)
+        if sh != H:
+            parts['inst_ny'] = _nearest_table_generic(H, sh).numpy().astype(np.int32)
+    if use_inst:
+        parts['inst'] = addresses(maps['inst'], torch.int32 if any(wide) else torch.uint8)
+    if opt.feat_pose:
+        present = [t if js is not None else None for t, js in zip(maps['pose_inst'], jsons)]
+        parts['pose'] = addresses(present)
+        parts['pose_has'], parts['pose_val'] = _pose_tables(opt, dataset, [js if t is not None else None
+                                                                           for t, js in zip(maps['pose_inst'], jsons)])
+    if opt.feat_normal:
+        parts['normal'] = addresses(maps['normal'])
+    with torch.cuda.device(dev):
+        d = _upload(dev, parts)
+        xtab = (d['xmin'], d['xk']) if sw != W else None
+        ytab = (d['ymin'], d['yk']) if sh != H else None
+        out = {'label': 0, 'inst': 0, 'image': 0, 'pose': 0, 'normal': 0}
+        out['image'] = _ops.assemble_planes(d['image'], items, d['items'], xtab, ytab, d['lut'], 3, H, W, sh, sw, h, w)
+        if opt.feat_normal:   # "bias caused by 0..256 instead 0..255" (vkitti_dataset.py:125, cityscapes_dataset.py:98)
+            out['normal'] = _ops.assemble_planes(d['normal'], items, d['items'], xtab, ytab, d['lut'], 3, H, W, sh, sw, h, w,
+                                                 add=np.float32(1 / 255))
+        label, inst, pose, missing = _ops.assemble_maps(
+            d['segm'], d.get('inst'), d.get('pose'), items, d['items'], d.get('nx'), d.get('ny'), d['tabs'], inst_mode, H, W, sh,
+            sw, h, w, wrap16=inst_wrap_int16, pose_has=d.get('pose_has'), pose_val=d.get('pose_val'),
+            min_area=MIN_POSE_AREA[dataset], inst_nx=d.get('inst_nx'), inst_ny=d.get('inst_ny'))
+    out['label'], out['missing'] = label, missing
+    if use_inst:
+        out['inst'] = inst
+    if opt.feat_pose:
+        out['pose'] = pose
+    return out

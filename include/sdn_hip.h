@@ -70,9 +70,11 @@ const char* sdn_last_error(void);
  * sdn_perspective_transform*, new arguments of sdn_in_apply / sdn_in_bwd / sdn_act_bwd / sdn_render_maps_*; r05: struct sdn_op
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
  * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
- * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added).  A binding must compare sdn_version() with
- * the SDN_ABI_VERSION it was written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong size. */
-#define SDN_ABI_VERSION 13
+ * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
+ * added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that
+ * answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
+ * size. */
+#define SDN_ABI_VERSION 14
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -573,6 +575,50 @@ int sdn_scene_id_stats(const int32_t* scene, const int32_t* disparity, int categ
                        void* workspace, sdnStream stream);
 int sdn_scene_id_planes(const int32_t* scene, const int32_t* disparity, const int32_t* ids, const int32_t* thr, int n, int H, int W,
                         float* masks, uint32_t* ignore_cover, float* ignores, sdnStream stream);
+
+/* ---- the textural loader's item on the device, batched: textural/data/base_dataset.py:41-104 (get_transform, __scale_width,
+ * __crop, __make_power_2, __flip) with vkitti_dataset.py:44-129 and cityscapes_dataset.py:32-111, which run per item with PIL
+ * and numpy on the host ----------------------------------------------------------------------------------------------------
+ * All B items of a call share the source size [H, W], the options and so the scaled size [sh, sw] (the one resize of the mode:
+ * Scale, __scale_width or __make_power_2) and the output size [h, w]; items_host / items: the same int32 [B, 4] rows (crop x1,
+ * y1, flip 0 / 1, unused) on the HOST (validated: x1, y1 >= 0) and on the DEVICE.  An output pixel (y, x) is the scaled image's
+ * pixel (y1 + y, x1 + (flip ? w - 1 - x : x)), 0 where that lies beyond [sh, sw] (PIL's crop).  Only the window is computed.
+ * The per-item map addresses are DEVICE int64 [B] tables, so that one host-to-device copy carries every table of a call.
+ *
+ * sdn_assemble_planes (base_dataset.py:41-66 for the image and the normal map; vkitti_dataset.py:63-66, 121-127,
+ * cityscapes_dataset.py:48-52, 95-100): src[b] = address of a DEVICE uint8 [C, H, W] map, 0 = the map is absent and the item's
+ * planes are 0.0.  Pillow's ImagingResample, bit for bit: xmin [sw] / xk [sw, xks] and ymin [sh] / yk [sh, yks] are
+ * precompute_coeffs' first source index and normalize_coeffs_8bpc's 22-bit weights (0 beyond a window) per scaled column / row;
+ * xks == 0 exactly when sw == W (no horizontal pass), yks == 0 exactly when sh == H.  Then lut [256] (ToTensor: float32(k) / 255
+ * computed on the host), (v - mean) / std when normalize, + add when bias (the normal branch's 1 / 255).  out fp32
+ * [B, C, h, w].  SDN_EINVAL when yks source rows of w bytes do not fit the 32 KiB LDS tile.  One launch.
+ *
+ * sdn_assemble_maps (NEAREST: vkitti_dataset.py:52-57, 68-118, cityscapes_dataset.py:41-42, 55-93, 102-105): segm[b], inst[b],
+ * pose[b] = addresses of DEVICE uint8 [H, W] maps (inst[b] int32 [H, W] when inst_mode is 3); inst[b] == 0: the loader's
+ * FileNotFoundError branch, inst = label (inst_mode 3, whose output is an integer tensor: the item's inst is 0; mix nothing
+ * there); pose[b] == 0: "no cars", the pose plane is 0.  nx [sw] / ny [sh]: ImagingScaleAffine's source index per scaled
+ * column / row, NULL exactly when the size does not change.  inst_nx [sw] / inst_ny [sh] (each may be NULL: nx / ny; non-NULL
+ * only where that size changes, inst_mode 3 only): the same for an instance map whose image mode Pillow resizes by its generic
+ * transform (mode 'I;16': int(a (x + 0.5)) on every axis that changes, instead of the running sum).  tabs fp32 [4, 256] by raw
+ * value: the label of a segm value, the label where the instance value is 0 (inst_mode 2; vkitti_dataset.py:75-78), the value that fills such an
+ * instance, the instance value of an inst byte.  inst_mode: 0 no instance output (inst, inst_out may be NULL), 1 inst =
+ * tabs[3][i], 2 the same with zeros filled, 3 the int32 map handed through; inst_out [B, 1, h, w] fp32, for mode 3 int32, or
+ * int16 when wrap16 (torchvision's ToTensor reads a mode 'I;16' image through np.int16).  label fp32 [B, 1, h, w].
+ * The pose plane (pose_out non-NULL; else pose, pose_has, pose_val, counts may be NULL): counts DEVICE int32 [B, 256] receives
+ * the number of transformed pixels per raw pose id (integer atomics, aggregated per workgroup in LDS); a second launch paints
+ * pose_out [B, pose_channels, h, w] 32-bit words = pose_val [B, 256, pose_channels] (int32 bins, or the bits of fp32 cos, sin) of
+ * every id != 0 whose count is >= min_area (cityscapes_dataset.py:82: 256; vkitti: 1) and pose_has [B, 256] is set; the pixels
+ * of such an id without a record are painted 0 and counted in missing int32 [B] (the reference raises KeyError there).
+ * The call clears counts and missing itself; nothing is copied to the host. */
+int sdn_assemble_planes(const int64_t* src, const int32_t* items_host, const int32_t* items, const int32_t* xmin,
+                        const int32_t* xk, int xks, const int32_t* ymin, const int32_t* yk, int yks, const float* lut, int B, int C,
+                        int H, int W, int sh, int sw, int h, int w, int normalize, float mean, float std, int bias, float add,
+                        float* out, sdnStream stream);
+int sdn_assemble_maps(const int64_t* segm, const int64_t* inst, const int64_t* pose, const int32_t* items_host,
+                      const int32_t* items, const int32_t* nx, const int32_t* ny, const int32_t* inst_nx, const int32_t* inst_ny,
+                      const float* tabs, int inst_mode, int wrap16, int B, int H, int W, int sh, int sw, int h, int w, float* label, void* inst_out, const int32_t* pose_has,
+                      const void* pose_val, int pose_channels, int min_area, void* pose_out, int32_t* counts, int32_t* missing,
+                      sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
