@@ -1198,3 +1198,80 @@ def assemble_maps(segm, inst, pose, items_host, items, nx, ny, tabs, inst_mode, 
                                       ptr(label), ptr(inst_out), ptr(pose_has) if ch else None, ptr(pose_val) if ch else None,
                                       ch if ch else 1, int(min_area), ptr(pose_out), ptr(counts), ptr(missing), stream()))
     return label, inst_out, pose_out, missing
+
+
+TRAIN_ITEM_INTS = 12   # one row of sdn_train_crops's item table
+TRAIN_BRIGHTNESS, TRAIN_CONTRAST, TRAIN_SATURATION, TRAIN_HUE = 0, 1, 2, 3
+
+
+def train_rois(scenes_u8, items):
+    """The rois and pixel counts of B (frame, colour code) pairs over several frames in one call (sdn_train_rois;
+    derender3d/datasets.py:345-347 per object on the host): scenes_u8 uint8 [Fr, H, W, 3] CUDA, items int32 [B, 4] CUDA rows
+    (frame index, r, g, b).  Returns table int32 [B, 5] CUDA = (first row, first column, last row + 1, last column + 1, area) of
+    all(scenes[frame] == code, axis 2); a code that matches nothing (or a frame index outside Fr) has the invalid row
+    (INT_MAX, INT_MAX, 0, 0, 0) of scene_gt_masks.  Nothing is copied to the host."""
+    scenes_u8 = want(scenes_u8, torch.uint8, 'scenes_u8')
+    items = want(items, torch.int32, 'items')
+    if scenes_u8.dim() != 4 or scenes_u8.shape[3] != 3 or scenes_u8.shape[0] < 1:
+        raise ValueError('scenes_u8 must be uint8 [Fr, H, W, 3], got %s' % (tuple(scenes_u8.shape),))
+    if items.dim() != 2 or items.shape[1] != 4 or items.shape[0] < 1:
+        raise ValueError('items must be int32 [B, 4] with B >= 1, got %s' % (tuple(items.shape),))
+    if items.device != scenes_u8.device:
+        raise ValueError('items is on %s, scenes_u8 on %s' % (items.device, scenes_u8.device))
+    Fr, H, W, _ = scenes_u8.shape
+    B = items.shape[0]
+    with torch.cuda.device(items.device):
+        table = torch.empty(B, 5, dtype=torch.int32, device=items.device)
+        check(lib().sdn_train_rois(ptr(scenes_u8), ptr(items), Fr, B, H, W, ptr(table), stream()))
+    return table
+
+
+def train_crops(frames_u8, scenes_u8, rois_host, objs_host, items_host, tables, items, nearer, image_size=224, mask_size=256,
+                mean=(0.5, 0.5, 0.5), std=(0.25, 0.25, 0.25)):
+    """The crops of B training items over several frames (sdn_train_crops; derender3d/datasets.py:141-172, 390-391, 415-417):
+    crop_square + colour jitter + PIL bilinear resize + to_tensor (+ Normalize for the image), bit for bit.  frames_u8 uint8
+    [Fr, 3, H, W], scenes_u8 uint8 [Fr, H, W, 3] CUDA; rois_host numpy int32 [B, 4]; objs_host numpy int32 [B, 12] and tables =
+    (objs, bounds, kk8) its CUDA copy with Pillow's tables (derender3d.scene.crop_tables); items_host numpy int32 [B, 12] and
+    items its CUDA copy (derender3d.train_items.item_table); nearer uint8 [total, 3] CUDA, the items' nearer codes (may be
+    empty).  Returns (images [B,3,S_i,S_i], masks [B,1,S_m,S_m], ignores [B,1,S_m,S_m]).  Nothing is copied to the host."""
+    frames_u8 = want(frames_u8, torch.uint8, 'frames_u8')
+    scenes_u8 = want(scenes_u8, torch.uint8, 'scenes_u8')
+    if frames_u8.dim() != 4 or frames_u8.shape[1] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError('frames_u8 must be uint8 [Fr, 3, H, W], got %s' % (tuple(frames_u8.shape),))
+    Fr, _, H, W = frames_u8.shape
+    if tuple(scenes_u8.shape) != (Fr, H, W, 3):
+        raise ValueError('scenes_u8 must be uint8 [%d, %d, %d, 3], got %s' % (Fr, H, W, tuple(scenes_u8.shape)))
+    rois_host = np.ascontiguousarray(rois_host, dtype=np.int32)
+    objs_host = np.ascontiguousarray(objs_host, dtype=np.int32)
+    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
+    if rois_host.ndim != 2 or rois_host.shape[1] != 4 or rois_host.shape[0] < 1:
+        raise ValueError('rois must be [B, 4] with B >= 1, got %s' % (rois_host.shape,))
+    B = rois_host.shape[0]
+    if objs_host.shape != (B, 12) or items_host.shape != (B, TRAIN_ITEM_INTS):
+        raise ValueError('objs_host must be [%d, 12] and items_host [%d, %d], got %s, %s'
+                         % (B, B, TRAIN_ITEM_INTS, objs_host.shape, items_host.shape))
+    objs, bounds, kk8 = (want(t, torch.int32, name) for t, name in zip(tables, ('objs', 'bounds', 'kk8')))
+    items = want(items, torch.int32, 'items')
+    nearer = want(nearer, torch.uint8, 'nearer')
+    if tuple(objs.shape) != (B, 12) or tuple(items.shape) != (B, TRAIN_ITEM_INTS):
+        raise ValueError('objs must be [%d, 12] and items [%d, %d], got %s, %s'
+                         % (B, B, TRAIN_ITEM_INTS, tuple(objs.shape), tuple(items.shape)))
+    if bounds.dim() != 2 or bounds.shape[1] != 2 or kk8.dim() != 1:
+        raise ValueError('bounds must be [M, 2] and kk8 [K], got %s, %s' % (tuple(bounds.shape), tuple(kk8.shape)))
+    if nearer.dim() != 2 or nearer.shape[1] != 3:
+        raise ValueError('nearer must be uint8 [total, 3], got %s' % (tuple(nearer.shape),))
+    dev = frames_u8.device
+    for t, name in ((scenes_u8, 'scenes_u8'), (objs, 'objs'), (bounds, 'bounds'), (kk8, 'kk8'), (items, 'items'), (nearer, 'nearer')):
+        if t.device != dev:
+            raise ValueError('%s is on %s, frames_u8 on %s' % (name, t.device, dev))
+    with torch.cuda.device(dev):
+        images = torch.empty(B, 3, image_size, image_size, device=dev)
+        masks = torch.empty(B, 1, mask_size, mask_size, device=dev)
+        ignores = torch.empty(B, 1, mask_size, mask_size, device=dev)
+        work = torch.empty(B, dtype=torch.int64, device=dev)
+        check(lib().sdn_train_crops(ptr(frames_u8), ptr(scenes_u8), Fr, H, W, rois_host.ctypes.data, objs_host.ctypes.data, ptr(objs),
+                                    items_host.ctypes.data, ptr(items), B, ptr(bounds), bounds.shape[0], ptr(kk8), kk8.shape[0],
+                                    ptr(nearer) if nearer.shape[0] else None, nearer.shape[0], image_size, mask_size,
+                                    float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
+                                    ptr(work), ptr(images), ptr(masks), ptr(ignores), stream()))
+    return images, masks, ignores

@@ -71,10 +71,10 @@ const char* sdn_last_error(void);
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
  * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
- * added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was written against and refuse a library that
- * answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
+ * added; 15: sdn_train_rois, sdn_train_crops added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 14
+#define SDN_ABI_VERSION 15
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -619,6 +619,47 @@ int sdn_assemble_maps(const int64_t* segm, const int64_t* inst, const int64_t* p
                       const float* tabs, int inst_mode, int wrap16, int B, int H, int W, int sh, int sw, int h, int w, float* label, void* inst_out, const int32_t* pose_has,
                       const void* pose_val, int pose_channels, int min_area, void* pose_out, int32_t* counts, int32_t* missing,
                       sdnStream stream);
+
+/* ---- the training items of the geometric branch, batched over several frames: geometric/derender3d/datasets.py:332-420
+ * (VKitti.__getitem__), :37-46 (roi_jitter), :141-172 (transform_rgb / _mask / _ignore with Transforms.color_jitter) and
+ * data_loader.py:17-37 (collate_fn), which run per object with numpy and PIL on the host ----------------------------------------
+ * sdn_train_rois (datasets.py:345-347): scenes DEVICE uint8 [Fr, H, W, 3], items DEVICE int32 [B, 4] rows (frame index, r, g, b)
+ * -> table DEVICE int32 [B, 5] rows (y0, x0, y1, x1, area) of all(scenes[frame] == code, axis 2): mask_to_roi's box (last index
+ * + 1) and the pixel count.  A code that matches no pixel, or a frame index outside [0, Fr), leaves the empty row of
+ * sdn_scene_gt_masks, (INT_MAX, INT_MAX, 0, 0) with area 0.  Several items may name one frame.  The call clears the table;
+ * integer atomics only (the result does not depend on scheduling); nothing is copied to the host.
+ *
+ * sdn_train_crops (datasets.py:141-172, 390-391, 415-417): for B items in one launch, after a statistics launch when an item's
+ * jitter holds contrast,
+ *   images  [B, 3, image_size, image_size]  from frames uint8 [Fr, 3, H, W], outside the frame 127; the item's colour jitter on
+ *           every pixel of the s x s window (fill and quirk pixels included, as PIL sees them) BEFORE the resize; then
+ *           ((u8 / 255) - mean[c]) / std[c] in three fp32 operations
+ *   masks   [B, 1, mask_size, mask_size]    scenes[frame] == the item's code, outside 0, value u8 / 255
+ *   ignores [B, 1, mask_size, mask_size]    count = the number of the item's nearer codes equal to the scene pixel (a code listed
+ *           twice counts twice), byte (255 count) & 255 as np.uint8(255 * count) wraps, outside 255, value u8 / 255
+ * with the window, the padding quirk and Pillow's resize of sdn_scene_crops, bit for bit; objs / objs_host: its object table
+ * [B, 12] on the DEVICE and on the HOST, rois_host HOST int32 [B, 4].  items / items_host: DEVICE and HOST int32 [B, 12] rows
+ * (frame index; code r | g << 8 | b << 16; first row and number of rows of the item's codes in `nearer`; number of ops 0 .. 4;
+ * the ops in order, 4 bits each from bit 0: 0 brightness, 1 contrast, 2 saturation, 3 hue, each at most once; the brightness,
+ * contrast and saturation factors as fp32 bits; the hue shift 0 .. 255; two unused ints).  nearer: DEVICE uint8 [n_nearer, 3].
+ * The ops are Pillow's as torchvision 0.2.1 applies drawn parameters: ImageEnhance.Brightness (Image.blend with black),
+ * .Contrast (blend with the solid grey int(mean(L) + 0.5) of the window as it is at that point of the order; the sum of L by
+ * 64-bit integer atomics in the statistics launch, the mean as (2 sum + n) / (2 n) in integers), .Color (blend with
+ * convert('L')), and convert('HSV'), H + shift modulo 256, convert('RGB').  No ops: exactly sdn_scene_crops' outputs.
+ * workspace: DEVICE, 8 B bytes aligned to 8 (the sums; when an item holds contrast the call clears it with one
+ * hipMemsetAsync on `stream` in front of the statistics launch).  The kernels clamp what they read out of `bounds` (first
+ * indices, tap counts, row runs); the rows of objs / items themselves are trusted as in sdn_scene_crops: only their HOST
+ * copies are validated, and a DEVICE table that differs from them reads out of bounds.  Validated on the host before any launch,
+ * SDN_EINVAL: an empty roi; a window table that is not crop_square's of the roi; a window wider than 4096 pixels (one source row
+ * must fit the staging tile), wider than 1448 with contrast (s^2 <= 2^21, where the integer mean is exact), or whose filter does
+ * not fit the 12 KiB row tile of a channel; a frame index outside [0, Fr); nearer rows outside [0, n_nearer]; an op listed
+ * twice or unknown; a resampling table outside the n_bounds rows of `bounds` / n_kk8 elements of `kk8`. */
+int sdn_train_rois(const uint8_t* scenes, const int32_t* items, int Fr, int B, int H, int W, int32_t* table, sdnStream stream);
+int sdn_train_crops(const uint8_t* frames, const uint8_t* scenes, int Fr, int H, int W, const int32_t* rois_host,
+                    const int32_t* objs_host, const int32_t* objs, const int32_t* items_host, const int32_t* items, int B,
+                    const int32_t* bounds, int n_bounds, const int32_t* kk8, int n_kk8, const uint8_t* nearer, int n_nearer,
+                    int image_size, int mask_size, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                    void* workspace, float* images, float* masks, float* ignores, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
