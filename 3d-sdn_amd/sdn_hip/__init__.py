@@ -18,7 +18,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', 'lib', 'libsdn_hip.so'))
 RGB, ALPHA, DEPTH, AA, FACE_COLOR, SAVE_MAPS, ACCUMULATE, SERIAL_EDGES, STREAM_FACES, COUNT_WORK = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 K1_COVERAGE = 4096   # SDN_K1_COVERAGE: the reference's default ("unsafe") forward kernel's coverage rule, deterministic ties
 
-ABI_VERSION = 15   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
+ABI_VERSION = 16   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
 
 _lib = None
 _lock = threading.Lock()
@@ -109,6 +109,9 @@ def _declare(L):
     sig['sdn_assemble_maps'] = [_vp] * 10 + [_ci] * 9 + [_vp] * 4 + [_ci, _ci] + [_vp] * 4
     sig['sdn_train_rois'] = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
     sig['sdn_train_crops'] = [_vp, _vp, _ci, _ci, _ci] + [_vp] * 5 + [_ci, _vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci] + [_cf] * 6 + [_vp] * 5
+    sig['sdn_train_losses_scratch'] = [_ci, _ci, _cl, ctypes.POINTER(_sz)]
+    sig['sdn_train_losses_fwd'] = [_vp] * 7 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp]
+    sig['sdn_train_losses_bwd'] = [_vp] * 6 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd] + [_vp] * 9 + [_vp]
     sig['sdn_perspective_transform_scratch'] = [_ci, _ci, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
     sig['sdn_perspective_transform'] = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
     sig['sdn_perspective_transform_bwd'] = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
@@ -181,7 +184,7 @@ def exported_symbols():
             'sdn_pose_params_bwd', 'sdn_composite_frame', 'sdn_edit_assemble', 'sdn_scene_cover', 'sdn_scene_crops', 'sdn_scene_edit',
             'sdn_unmold_masks', 'sdn_scene_gt_masks', 'sdn_scene_paint2d',
             'sdn_scene_id_workspace_bytes', 'sdn_scene_id_stats', 'sdn_scene_id_planes', 'sdn_assemble_planes', 'sdn_assemble_maps',
-            'sdn_train_rois', 'sdn_train_crops',
+            'sdn_train_rois', 'sdn_train_crops', 'sdn_train_losses_scratch', 'sdn_train_losses_fwd', 'sdn_train_losses_bwd',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',
@@ -247,6 +250,13 @@ def perspective_transform_scratch(n, V):
     kb, ab = _sz(0), _sz(0)
     check(lib().sdn_perspective_transform_scratch(n, V, ctypes.byref(kb), ctypes.byref(ab)))
     return kb.value, ab.value
+
+
+def train_losses_scratch(B, R, nffd):
+    """bytes of the `scratch` of sdn_train_losses_fwd / _bwd, asked of the library"""
+    n = _sz(0)
+    check(lib().sdn_train_losses_scratch(B, R, nffd, ctypes.byref(n)))
+    return n.value
 
 
 def raster_bwd_workspace(bs, nf, S, device):

@@ -573,6 +573,71 @@ class SilhouetteLossFn(torch.autograd.Function):
         return gm, None, (gf.reshape(ctx.ffd_shape) if gf is not None else None), None
 
 
+_train_loss_sizes = {}
+
+
+def _train_losses_scratch(B, R, nffd):
+    """bytes of sdn_train_losses_*'s scratch: the library's own answer, remembered per shape"""
+    r = _train_loss_sizes.get((B, R, nffd))
+    if r is None:
+        from . import train_losses_scratch
+        if len(_train_loss_sizes) > 256:
+            _train_loss_sizes.clear()
+        r = _train_loss_sizes[(B, R, nffd)] = train_losses_scratch(B, R, nffd)
+    return r
+
+
+class TrainLossesFn(torch.autograd.Function):
+    """The loss dict of BaseNet.step_batch (geometric/scripts/main.py:114-154) as one [7] tensor: theta_delta_loss,
+    translation2d_loss, scale_loss, depth_loss, class_reward, mask_loss, ffd_coeff_reg -- sdn_train_losses_fwd / _bwd
+    (include/sdn_hip.h), forward in two launches, backward in one; `targets` selects the items of each loss on the device.
+    The tensors of a group `mode` does not ask for may be None; its slots are 0."""
+
+    @staticmethod
+    def forward(ctx, mode, mask_weight, ffd_coeff_reg, p_theta_deltas, p_translation2ds, p_log_scales, p_log_depths,
+                p_class_log_probs, p_masks, p_ffd, thetas, translation2ds, log_scales, log_depths, masks, ignores, targets):
+        names = ('_theta_deltas', '_translation2ds', '_log_scales', '_log_depths', '_class_log_probs', '_masks', '_ffd_coeffs',
+                 'thetas', 'translation2ds', 'log_scales', 'log_depths', 'masks', 'ignores')
+        given = (p_theta_deltas, p_translation2ds, p_log_scales, p_log_depths, p_class_log_probs, p_masks, p_ffd, thetas,
+                 translation2ds, log_scales, log_depths, masks, ignores)
+        td, t2, ls, ld, lp, pm, ff, th, bt2, bls, bld, bm, bi = (_f32(t, n) for t, n in zip(given, names))
+        tg = want(targets, torch.int64, 'targets')
+        B = tg.shape[0]
+        R = pm.shape[-1] if pm is not None else 1
+        S = bm.shape[-1] if bm is not None else R
+        nffd = ff.numel() if ff is not None else 0
+        scratch = torch.empty(_train_losses_scratch(B, R, nffd), dtype=torch.uint8, device=tg.device)
+        out = torch.empty(7, dtype=torch.float32, device=tg.device)
+        cfg = (B, R, S, int(mode), float(mask_weight), float(ffd_coeff_reg))
+        check(lib().sdn_train_losses_fwd(ptr(td), ptr(t2), ptr(ls), ptr(ld), ptr(lp), ptr(pm), ptr(ff), nffd, ptr(th), ptr(bt2),
+                                         ptr(bls), ptr(bld), ptr(bm), ptr(bi), ptr(tg), *cfg, ptr(scratch), ptr(out), stream()))
+        ctx.save_for_backward(td, t2, ls, ld, pm, ff, th, bt2, bls, bld, bm, bi, tg, scratch)
+        ctx.cfg = cfg
+        ctx.lp = (lp.shape, lp.device) if lp is not None else None
+        ctx.shapes = [t.shape if t is not None else None for t in given[:7]]
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        td, t2, ls, ld, pm, ff, th, bt2, bls, bld, bm, bi, tg, scratch = ctx.saved_tensors
+        src = (td, t2, ls, ld, None, pm, ff)
+        grads = []
+        for k, (need, t) in enumerate(zip(ctx.needs_input_grad[3:10], src)):
+            if k == 4:   # _class_log_probs: its gradient needs m_i alone
+                grads.append(torch.empty(ctx.lp[0], dtype=torch.float32, device=ctx.lp[1]) if need and ctx.lp is not None else None)
+            else:
+                grads.append(torch.empty_like(t) if need and t is not None else None)
+        if all(x is None for x in grads):
+            return (None,) * 17
+        go = g.contiguous()
+        nffd = ff.numel() if ff is not None else 0
+        check(lib().sdn_train_losses_bwd(ptr(td), ptr(t2), ptr(ls), ptr(ld), ptr(pm), ptr(ff), nffd, ptr(th), ptr(bt2), ptr(bls),
+                                         ptr(bld), ptr(bm), ptr(bi), ptr(tg), *ctx.cfg, ptr(scratch), ptr(go),
+                                         *[ptr(x) for x in grads], stream()))
+        grads = [x.reshape(s) if x is not None else None for x, s in zip(grads, ctx.shapes)]
+        return (None, None, None) + tuple(grads) + (None,) * 7
+
+
 class PerspectiveTransformFn(torch.autograd.Function):
     """(vertices [n,V,3], zooms [n,1]) = zoom_fit(shear(R(q) (v * s) + t))  -- derender3d/models/transforms.py:102-158 for
     a whole frame in two launches (forward) / three (backward) instead of ~25 element-wise ops and a batched GEMM."""

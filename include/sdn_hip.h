@@ -71,10 +71,11 @@ const char* sdn_last_error(void);
  * with 40 ints, sdn_render_maps_bwd takes bg; 9: sdn_edit_assemble added; 10: sdn_scene_cover, sdn_scene_crops,
  * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
- * added; 15: sdn_train_rois, sdn_train_crops added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
+ * added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 15
+#define SDN_ABI_VERSION 16
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -423,6 +424,49 @@ int sdn_silhouette_loss_fwd(const float* masks, const float* target, const float
                             double* sums, float* out, sdnStream stream);
 int sdn_silhouette_loss_bwd(const float* masks, const float* target, const float* ignore, long n, const float* ffd, long nffd,
                             const double* sums, const float* grad_out, float* grad_masks, float* grad_ffd, sdnStream stream);
+/* The loss dict of a training step of the geometric branch, geometric/scripts/main.py:114-154 (BaseNet.step_batch with
+ * BaseNet.partial, :97-112, and Transforms.pad_like, derender3d/datasets.py:29-33), which the reference writes as torch
+ * expressions: per loss a torch.nonzero + numel() branch and an isnan().any() branch (two host waits each, six losses), two
+ * padded copies of the batch's masks / ignore maps at the render size and about a dozen element-wise launches each way.
+ * Here `targets` is data: B items, rendered masks R x R, target masks / ignore maps S x S, p = (R - S) / 2 (R - S even and
+ * >= 0, else SDN_EINVAL: pad_like pads (R - S) // 2 on both sides and an odd difference does not line up).
+ *   sel_g = targets & 1 (TargetType.geometry), n_g items;  sel_r = targets & 2 (TargetType.reproject), n_r items
+ *   mode & 1:  out[0] theta_delta_loss   = mean over sel_g x 2 of (_theta_deltas - (cos thetas, sin thetas))^2  (cos / sin in
+ *                                          double, rounded once to fp32)
+ *              out[1] translation2d_loss, out[2] scale_loss, out[3] depth_loss: mean over sel_g x (2, 3, 1) of (pred - batch)^2
+ *              n_g = 0: exactly 0, no gradient (the torch.tensor(0.0) branch of `partial`)
+ *   mode & 2:  m_i = mask_weight / R^2 * sum_{y,x} (1 - ignores_i[clamp(y - p), clamp(x - p)]) (_masks_i[y, x] - masks_i[y - p, x - p])^2
+ *              with masks = 0 outside [0, S)^2 (pad_like 'constant') and the ignore index clamped to [0, S - 1] ('replicate');
+ *              the padding is index arithmetic, no copy is made
+ *              out[4] class_reward = mean over sel_r of _class_log_probs_i * m_i   (m_i detached: gradient to the log-probs only)
+ *              out[5] mask_loss    = mean over sel_r of m_i;   n_r = 0: both exactly 0, no gradient
+ *              out[6] ffd_coeff_reg = ffd_coeff_reg * mean(_ffd_coeffs^2) over ALL items (the reference does not mask it)
+ *   the slots of a group `mode` does not ask for are 0 and its pointers may be NULL.  Items outside sel_r are not read.
+ * fwd: one launch of per-block fp64 partial sums (grid: item x chunk of rows; 16-byte loads of _masks when R % 4 == 0, of masks /
+ * ignores when S % 4 == 0 and p % 4 == 0 too, and the pointers allow; scalar loads otherwise) -- skipped when mode lacks
+ * reproject -- and one finishing wave that adds them in block order: no atomics, no memset, the same bits every run.
+ * bwd: ONE launch from grad_out[7] (DEVICE):
+ *   grad_masks[i,y,x] = grad_out[5] [i in sel_r] mask_weight 2 (1 - ign) (_masks - masks) / (n_r R^2), zeros elsewhere
+ *   grad_class_log_probs[i] = grad_out[4] [i in sel_r] m_i / n_r;   grad_ffd = grad_out[6] 2 ffd_coeff_reg ffd / nffd
+ *   the four head gradients grad_out[k] 2 (pred - target) / (cols n_g) on the rows of sel_g, zeros elsewhere
+ * any grad_* may be NULL (not wanted); every element of a non-NULL one is written.
+ * scratch: DEVICE, sdn_train_losses_scratch(B, R, nffd) bytes aligned to 8, no initialisation needed, kept between the fwd
+ * call and its bwd call (n_g, n_r, m_i live there).  All tensors fp32 DEVICE arrays, dense; targets int64 [B].
+ * _theta_deltas / _translation2ds / translation2ds [B,2], _log_scales / log_scales [B,3], _log_depths / log_depths / thetas
+ * [B,1], _class_log_probs [B], _masks [B,1,R,R], masks / ignores [B,1,S,S], _ffd_coeffs nffd elements. */
+int sdn_train_losses_scratch(int B, int R, long nffd, size_t* bytes);
+int sdn_train_losses_fwd(const float* p_theta_deltas, const float* p_translation2ds, const float* p_log_scales,
+                         const float* p_log_depths, const float* p_class_log_probs, const float* p_masks, const float* p_ffd,
+                         long nffd, const float* thetas, const float* translation2ds, const float* log_scales,
+                         const float* log_depths, const float* masks, const float* ignores, const int64_t* targets, int B, int R,
+                         int S, int mode, double mask_weight, double ffd_coeff_reg, void* scratch, float* out, sdnStream stream);
+int sdn_train_losses_bwd(const float* p_theta_deltas, const float* p_translation2ds, const float* p_log_scales,
+                         const float* p_log_depths, const float* p_masks, const float* p_ffd, long nffd, const float* thetas,
+                         const float* translation2ds, const float* log_scales, const float* log_depths, const float* masks,
+                         const float* ignores, const int64_t* targets, int B, int R, int S, int mode, double mask_weight,
+                         double ffd_coeff_reg, const void* scratch, const float* grad_out, float* grad_theta_deltas,
+                         float* grad_translation2ds, float* grad_log_scales, float* grad_log_depths, float* grad_class_log_probs,
+                         float* grad_masks, float* grad_ffd, sdnStream stream);
 /* Pose parameters of a frame's objects, derender3d/models/__init__.py:106-116: quat[n,4] = (cos(theta/2), 0, sin(theta/2), 0),
  * scales[n,3] = exp(log_scales); and the adjoint (g_quat / g_scales may be NULL = no gradient arrived). */
 int sdn_pose_params(const float* theta, const float* log_scales, int n, float* quat, float* scales, sdnStream stream);
