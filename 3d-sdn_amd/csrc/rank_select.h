@@ -1,0 +1,44 @@
+// The rank search of the exact radix selects (scene_ids.hip per id of one frame, train_hybrid.hip per item of a batch).
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+namespace sdn {
+
+// The bin of a 256-bin histogram that holds the element of rank `rank` (zero-based, ascending) and the rank inside that bin,
+// by one wave: four bins per lane, an inclusive scan over the lanes.  (0, 0) when the histogram holds fewer elements.
+__device__ __forceinline__ void ids_find(const int32_t* hist, long rank, int lane, int* bin, int* residual)
+{
+    int c[4];
+    int sum = 0;
+    for (int k = 0; k < 4; k++) {
+        c[k] = hist[4 * lane + k];
+        sum += c[k];
+    }
+    int incl = sum;
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    long before = incl - sum;
+    int b = 0, r = 0;
+    bool found = false;
+    if (rank >= before && rank < incl) {
+        for (int k = 0; k < 4 && !found; k++) {
+            if (rank < before + c[k]) {
+                found = true;
+                b = 4 * lane + k;
+                r = (int)(rank - before);
+            }
+            before += c[k];
+        }
+    }
+    const unsigned long long m = __ballot(found);
+    const int src = m ? __ffsll((long long)m) - 1 : 0;
+    *bin = __shfl(b, src, 64);
+    *residual = __shfl(r, src, 64);
+}
+
+}  // namespace sdn

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "rank_select.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -177,40 +178,6 @@ __global__ __launch_bounds__(ID_THREADS) void k_ids_pass_a(const int32_t* __rest
         const int c = s_hist[s][tid];
         if (c) atomicAdd(hist_hi + (size_t)j * ID_BINS + tid, c);
     }
-}
-
-// The bin of a 256-bin histogram that holds the element of rank `rank` (zero-based, ascending) and the rank inside that bin,
-// by one wave: four bins per lane, an inclusive scan over the lanes.  (0, 0) when the histogram holds fewer elements.
-__device__ __forceinline__ void ids_find(const int32_t* hist, long rank, int lane, int* bin, int* residual)
-{
-    int c[4];
-    int sum = 0;
-    for (int k = 0; k < 4; k++) {
-        c[k] = hist[4 * lane + k];
-        sum += c[k];
-    }
-    int incl = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    long before = incl - sum;
-    int b = 0, r = 0;
-    bool found = false;
-    if (rank >= before && rank < incl) {
-        for (int k = 0; k < 4 && !found; k++) {
-            if (rank < before + c[k]) {
-                found = true;
-                b = 4 * lane + k;
-                r = (int)(rank - before);
-            }
-            before += c[k];
-        }
-    }
-    const unsigned long long m = __ballot(found);
-    const int src = m ? __ffsll((long long)m) - 1 : 0;
-    *bin = __shfl(b, src, 64);
-    *residual = __shfl(r, src, 64);
 }
 
 __global__ __launch_bounds__(64) void k_ids_select(const int32_t* __restrict__ table, const int32_t* __restrict__ hist_hi, int32_t* sel)

@@ -28,46 +28,9 @@
 #include <cstdint>
 
 #include "sdn_common.h"
+#include "train_items_common.h"
 
 namespace sdn {
-
-constexpr int TI_BITS = 22;             // Pillow Resample.c: PRECISION_BITS = 32 - 8 - 2
-constexpr int TI_THREADS = 256;
-constexpr int TI_WAVES = TI_THREADS / 64;
-constexpr int TI_BAND = 8;              // output rows per workgroup
-// LDS of k_train_crops, per channel (the image kind uses three, the mask and ignore kinds one):
-//   staged source pixels   4 KiB: whole rows of the s-wide window, 4096 / s rows per pass (so s <= 4096)
-//   resampled rows         12 KiB: the band's horizontally resampled source rows, one byte per pixel; 12288 / S rows (54 at
-//                          224, 48 at 256; a band of 8 rows at the widest VKITTI window, 1242 -> 224, needs 49)
-// 48 KiB per workgroup: three workgroups (12 waves) per CU in the 160 KiB of a gfx950 CU.
-constexpr int TI_SRC_PIXELS = 4096;
-constexpr int TI_PLANE_BYTES = 12288;
-constexpr int TI_STAT_PIXELS = 2048;    // window pixels per workgroup of k_train_stats
-constexpr int TI_OBJ_INTS = 12;
-constexpr int TI_ITEM_INTS = 12;
-constexpr int TI_MAX_CONTRAST_SIDE = 1448;   // s^2 <= 2^21: where the integer mean equals int(sum / n + 0.5) in float64
-
-enum { TI_BRIGHTNESS = 0, TI_CONTRAST = 1, TI_SATURATION = 2, TI_HUE = 3 };
-
-struct TrainWin {   // one row of derender3d.scene.crop_tables' object table (the layout of sdn_scene_crops)
-    int oy, ox;                // frame coordinates of the window's first pixel
-    int s;                     // side of the square window
-    int xlim, ylim;            // frame coordinates where crop_square's padded image ends (beyond: 0)
-    int boff_i, koff_i, ksize_i;   // tables of the resize s -> image_size (ksize 0: s == image_size, no resampling)
-    int boff_m, koff_m, ksize_m;   // tables of the resize s -> mask_size
-    int pad;
-};
-
-struct TrainItem {  // one row of the item table
-    int frame;                 // index into frames / scenes
-    int code;                  // r | g << 8 | b << 16 of the object's colour in the scene image
-    int near_off, near_cnt;    // the item's nearer codes: rows near_off .. near_off + near_cnt of `nearer`
-    int nops;                  // ops of the colour jitter, 0 .. 4
-    int order;                 // op k in bits 4 k .. 4 k + 3
-    float fb, fc, fs;          // brightness, contrast, saturation factors
-    int hue;                   // added to H modulo 256
-    int pad0, pad1;
-};
 
 struct TrainParams {
     const uint8_t* frames;     // [Fr, 3, H, W]
@@ -82,111 +45,6 @@ struct TrainParams {
     float mean[3], std[3];
     float *images, *masks, *ignores;
 };
-
-__device__ __forceinline__ int ti_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-__device__ __forceinline__ int ti_wave_sum(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int ti_wave_min(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int ti_wave_max(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-// ---- Pillow's arithmetic ---------------------------------------------------------------------------------------------------
-// Image.blend(degenerate, image, alpha), one byte (Blend.c)
-__device__ __forceinline__ int ti_blend(int d, int v, float a)
-{
-    const float t = (float)d + a * (float)(v - d);
-    if (a >= 0.f && a <= 1.f) return (int)t;
-    return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
-}
-
-__device__ __forceinline__ int ti_luma(int r, int g, int b) { return (19595 * r + 38470 * g + 7471 * b + 32768) >> 16; }
-
-// C's round() of a value that is not negative: half away from zero, without forming x + 0.5
-__device__ __forceinline__ int ti_round(double x)
-{
-    const double f = floor(x);
-    return (int)f + ((x - f) >= 0.5 ? 1 : 0);
-}
-
-// convert('HSV'), H + shift modulo 256, convert('RGB') (Convert.c: rgb2hsv_row, hsv2rgb)
-__device__ __forceinline__ void ti_hue(int shift, int& r, int& g, int& b)
-{
-    const int maxc = max(r, max(g, b)), minc = min(r, min(g, b));
-    int uh = 0, us = 0;
-    const int uv = maxc;
-    if (minc != maxc) {
-        const float cr = (float)(maxc - minc);
-        const float s = cr / (float)maxc;
-        const float rc = (float)(maxc - r) / cr, gc = (float)(maxc - g) / cr, bc = (float)(maxc - b) / cr;
-        float h;
-        if (r == maxc) h = bc - gc;
-        else if (g == maxc) h = (float)(2.0 + (double)rc - (double)bc);
-        else h = (float)(4.0 + (double)gc - (double)rc);
-        double t = (double)h / 6.0 + 1.0;
-        if (t >= 1.0) t = t - 1.0;   // fmod(t, 1.0) for t in [5/6, 11/6]
-        h = (float)t;
-        uh = ti_clip8((int)((double)h * 255.0));
-        us = ti_clip8((int)((double)s * 255.0));
-    }
-    uh = (uh + shift) & 255;
-    if (us == 0) {
-        r = g = b = uv;
-        return;
-    }
-    const double h6 = (double)(float)uh * 6.0 / 255.0;
-    const int i = (int)floor(h6);
-    const float f = (float)(h6 - (double)(float)i);
-    const float fs = (float)((double)(float)us / 255.0);
-    const double v = (double)(float)uv;
-    const int p = ti_clip8(ti_round(v * (1.0 - (double)fs)));
-    const int q = ti_clip8(ti_round(v * (1.0 - (double)(fs * f))));
-    const int t = ti_clip8(ti_round(v * (1.0 - (double)fs * (1.0 - (double)f))));
-    switch (i % 6) {
-        case 0: r = uv; g = t; b = p; break;
-        case 1: r = q; g = uv; b = p; break;
-        case 2: r = p; g = uv; b = t; break;
-        case 3: r = p; g = q; b = uv; break;
-        case 4: r = t; g = p; b = uv; break;
-        default: r = uv; g = p; b = q; break;
-    }
-}
-
-// the ops [0, stop) of the item's order on one pixel; `grey` is the contrast op's solid grey
-__device__ __forceinline__ void ti_jitter(const TrainItem& it, int stop, int grey, int& r, int& g, int& b)
-{
-    for (int k = 0; k < stop; k++) {
-        const int op = (it.order >> (4 * k)) & 15;
-        if (op == TI_BRIGHTNESS) {
-            r = ti_blend(0, r, it.fb); g = ti_blend(0, g, it.fb); b = ti_blend(0, b, it.fb);
-        } else if (op == TI_CONTRAST) {
-            r = ti_blend(grey, r, it.fc); g = ti_blend(grey, g, it.fc); b = ti_blend(grey, b, it.fc);
-        } else if (op == TI_SATURATION) {
-            const int l = ti_luma(r, g, b);
-            r = ti_blend(l, r, it.fs); g = ti_blend(l, g, it.fs); b = ti_blend(l, b, it.fs);
-        } else {
-            ti_hue(it.hue, r, g, b);
-        }
-    }
-}
-
-// position of the contrast op in the order, -1 without
-__device__ __forceinline__ int ti_contrast_at(const TrainItem& it)
-{
-    for (int k = 0; k < it.nops; k++)
-        if (((it.order >> (4 * k)) & 15) == TI_CONTRAST) return k;
-    return -1;
-}
 
 // ---- the window's pixels as crop_square returns them ---------------------------------------------------------------------------
 // 0: beyond the padded image (PIL's crop gives 0), 1: padding (the fill value), 2: inside the frame, *p its offset in a plane
@@ -275,134 +133,38 @@ __global__ __launch_bounds__(TI_THREADS) void k_train_rois(const uint8_t* __rest
     }
 }
 
-// ---- the contrast mean -------------------------------------------------------------------------------------------------------
+// ---- the kernels: the shared bodies (train_items_common.h) on the call's frames and scenes ------------------------------------------
+struct TrainSrc {
+    const TrainParams& A;
+    const TrainWin& o;
+    const TrainItem& it;
+    __device__ __forceinline__ void rgb(int wy, int wx, int& r, int& g, int& b) const { ti_raw_rgb(A, o, it, wy, wx, r, g, b); }
+    __device__ __forceinline__ int map_byte(int kind, int wy, int wx) const { return ti_map_byte(A, o, it, kind, wy, wx); }
+    __device__ __forceinline__ float mean(int ch) const { return A.mean[ch]; }
+    __device__ __forceinline__ float stdev(int ch) const { return A.std[ch]; }
+};
+
 __global__ __launch_bounds__(TI_THREADS) void k_train_stats(const TrainParams A)
 {
     __shared__ int s_part[TI_WAVES];
-    const int n = blockIdx.y, tid = threadIdx.x;
+    const int n = blockIdx.y;
     const TrainItem it = A.items[n];
-    const int at = ti_contrast_at(it);
-    if (at < 0) return;
     const TrainWin o = A.objs[n];
-    if (o.s < 1 || o.s > TI_MAX_CONTRAST_SIDE) return;   // the launcher checked the host's copy of the table
-    const int total = o.s * o.s;
-    const int i0 = blockIdx.x * TI_STAT_PIXELS;
-    if (i0 >= total) return;
-    const int i1 = min(i0 + TI_STAT_PIXELS, total);
-    int acc = 0;   // at most 8 pixels of 255 per thread
-    for (int i = i0 + tid; i < i1; i += TI_THREADS) {
-        int r, g, b;
-        ti_raw_rgb(A, o, it, i / o.s, i % o.s, r, g, b);
-        ti_jitter(it, at, 0, r, g, b);
-        acc += ti_luma(r, g, b);
-    }
-    acc = ti_wave_sum(acc);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        int sum = 0;
-        for (int w = 0; w < TI_WAVES; w++) sum += s_part[w];
-        if (sum) atomicAdd(A.lsum + n, (unsigned long long)sum);
-    }
+    ti_stats_body(TrainSrc{A, o, it}, o, it, A.lsum + n, s_part);
 }
 
-// ---- the crops -----------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(TI_THREADS) void k_train_crops(const TrainParams A)
 {
     __shared__ uint8_t s_src[3 * TI_SRC_PIXELS];
     __shared__ uint8_t s_rows[3 * TI_PLANE_BYTES];
-    const int n = blockIdx.z, kind = blockIdx.y, tid = threadIdx.x;   // kind 0: image, 1: mask, 2: ignore
-    const bool img = kind == 0;
-    const int C = img ? 3 : 1;
-    const int S = img ? A.Si : A.Sm;
+    const int n = blockIdx.z, kind = blockIdx.y;   // kind 0: image, 1: mask, 2: ignore
+    const int S = kind == 0 ? A.Si : A.Sm;
     const int r0 = blockIdx.x * TI_BAND;
     if (r0 >= S) return;
-    const int r1 = min(r0 + TI_BAND, S);
     const TrainWin o = A.objs[n];
     const TrainItem it = A.items[n];
-    const int s = o.s;
-    if (s < 1 || s > TI_SRC_PIXELS) return;   // the launcher checked the host's copy of the table; uniform over the workgroup
-    const int ksize = img ? o.ksize_i : o.ksize_m;
-    float* out = img ? A.images + (size_t)n * 3 * S * S : (kind == 1 ? A.masks : A.ignores) + (size_t)n * S * S;
-    int grey = 0;
-    if (img && ti_contrast_at(it) >= 0) {   // int(mean(L) + 0.5) = (2 sum + n) / (2 n) in integers
-        const unsigned long long cnt = (unsigned long long)s * s;
-        grey = (int)((2ull * A.lsum[n] + cnt) / (2ull * cnt));
-    }
-
-    if (ksize == 0) {   // s == S: Pillow skips both passes
-        for (int i = tid; i < (r1 - r0) * S; i += TI_THREADS) {
-            const int y = r0 + i / S, x = i % S;
-            if (img) {
-                int c[3];
-                ti_raw_rgb(A, o, it, y, x, c[0], c[1], c[2]);
-                ti_jitter(it, it.nops, grey, c[0], c[1], c[2]);
-                for (int ch = 0; ch < 3; ch++)
-                    out[((size_t)ch * S + y) * S + x] = ((float)c[ch] / 255.f - A.mean[ch]) / A.std[ch];
-            } else {
-                out[(size_t)y * S + x] = (float)ti_map_byte(A, o, it, kind, y, x) / 255.f;
-            }
-        }
-        return;
-    }
-    const int* b = A.bounds + 2 * (img ? o.boff_i : o.boff_m);
-    const int* k = A.kk8 + (img ? o.koff_i : o.koff_m);
-    const int cap = TI_PLANE_BYTES / S;      // resampled source rows a plane holds (the launcher checked ksize < cap)
-    const int per = TI_SRC_PIXELS / s;       // whole source rows staged per pass (the launcher checked s <= 4096)
-    int ra = r0;
-    while (ra < r1) {
-        // the longest run of output rows from ra whose source rows fit the plane (uniform over the workgroup)
-        const int ybase = b[2 * ra];
-        int rb = ra + 1, yend = ybase + b[2 * ra + 1];
-        while (rb < r1 && b[2 * rb] + b[2 * rb + 1] - ybase <= cap) {
-            yend = max(yend, b[2 * rb] + b[2 * rb + 1]);
-            rb++;
-        }
-        const int rows = max(1, min(min(yend, s) - ybase, cap));
-        for (int c0 = 0; c0 < rows; c0 += per) {
-            const int cn = min(per, rows - c0);
-            // stage: the source rows ybase + c0 .. + cn of the window, jittered / tested once per pixel
-            for (int i = tid; i < cn * s; i += TI_THREADS) {
-                const int wy = min(ybase + c0 + i / s, s - 1), wx = i % s;
-                if (img) {
-                    int cr, cg, cb;
-                    ti_raw_rgb(A, o, it, wy, wx, cr, cg, cb);
-                    ti_jitter(it, it.nops, grey, cr, cg, cb);
-                    s_src[i] = (uint8_t)cr;
-                    s_src[TI_SRC_PIXELS + i] = (uint8_t)cg;
-                    s_src[2 * TI_SRC_PIXELS + i] = (uint8_t)cb;
-                } else {
-                    s_src[i] = (uint8_t)ti_map_byte(A, o, it, kind, wy, wx);
-                }
-            }
-            __syncthreads();
-            // horizontal pass out of the staged rows, rounded to uint8 as Pillow stores them
-            for (int i = tid; i < C * cn * S; i += TI_THREADS) {
-                const int ch = i / (cn * S), j = i - ch * (cn * S);
-                const int ry = j / S, x = j % S;
-                const int x0 = max(b[2 * x], 0), xc = min(b[2 * x + 1], ksize);
-                const uint8_t* src = s_src + ch * TI_SRC_PIXELS + ry * s;
-                int acc = 1 << (TI_BITS - 1);
-                for (int t = 0; t < xc; t++) acc += (int)src[min(x0 + t, s - 1)] * k[x * ksize + t];
-                s_rows[ch * TI_PLANE_BYTES + (c0 + ry) * S + x] = (uint8_t)ti_clip8(acc >> TI_BITS);
-            }
-            __syncthreads();
-        }
-        // vertical pass, to_tensor, Normalize
-        for (int i = tid; i < C * (rb - ra) * S; i += TI_THREADS) {
-            const int ch = i / ((rb - ra) * S), j = i - ch * ((rb - ra) * S);
-            const int y = ra + j / S, x = j % S;
-            const int y0 = b[2 * y] - ybase, yc = min(b[2 * y + 1], ksize);
-            const uint8_t* plane = s_rows + ch * TI_PLANE_BYTES;
-            int acc = 1 << (TI_BITS - 1);
-            for (int t = 0; t < yc; t++) acc += (int)plane[min(max(y0 + t, 0), rows - 1) * S + x] * k[y * ksize + t];
-            float v = (float)ti_clip8(acc >> TI_BITS) / 255.f;
-            if (img) v = (v - A.mean[ch]) / A.std[ch];
-            out[((size_t)ch * S + y) * S + x] = v;
-        }
-        __syncthreads();
-        ra = rb;
-    }
+    float* out = kind == 0 ? A.images + (size_t)n * 3 * S * S : (kind == 1 ? A.masks : A.ignores) + (size_t)n * S * S;
+    ti_crops_body(TrainSrc{A, o, it}, o, it, A.bounds, A.kk8, A.lsum + n, kind, S, r0, out, s_src, s_rows);
 }
 
 }  // namespace sdn

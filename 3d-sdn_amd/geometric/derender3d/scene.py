@@ -56,14 +56,18 @@ def crop_windows(rois, height, width):
 def crop_tables(rois, height, width, image_size, mask_size):
     """The host tables of sdn_scene_crops: (objs int32 [N, 12], bounds int32 [M, 2], kk8 int32 [K]).  One Pillow table
     (compositing.resample_tables + fixed_point) per distinct (window side, output size); none when they are equal, where
-    Pillow skips the resampling (ksize 0)."""
-    win = crop_windows(rois, height, width)
+    Pillow skips the resampling (ksize 0).  height, width: of the one frame, or one per roi (sdn_train_crops_mixed)."""
+    rois = np.asarray(rois, dtype=np.int64).reshape(-1, 4)
+    heights, widths = (np.broadcast_to(np.asarray(v, dtype=np.int64), (rois.shape[0],)) for v in (height, width))
     table, bounds_all, k8_all = {}, [], []
     nb = nk = 0
-    objs = np.zeros((win.shape[0], OBJ_INTS), dtype=np.int32)
-    for i in range(win.shape[0]):
-        s = int(win[i, 2])
-        objs[i, :5] = win[i]
+    objs = np.zeros((rois.shape[0], OBJ_INTS), dtype=np.int32)
+    for i in range(rois.shape[0]):
+        try:
+            objs[i, :5] = crop_windows(rois[i], int(heights[i]), int(widths[i]))[0]
+        except ValueError:
+            raise ValueError('roi %d (%d, %d, %d, %d) is empty' % ((i,) + tuple(rois[i].tolist())))
+        s = int(objs[i, 2])
         for col, size in ((5, image_size), (8, mask_size)):
             if s == size:
                 continue

@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, lib, ptr, raster_bwd_workspace,
-               raster_workspace, scene_id_workspace, stream, want)
+               raster_workspace, scene_id_workspace, stream, train_id_workspace, want)
 
 CAMERA_NONE, CAMERA_LOOK, CAMERA_LOOK_AT = 0, 1, 2
 
@@ -1339,4 +1339,70 @@ def train_crops(frames_u8, scenes_u8, rois_host, objs_host, items_host, tables, 
                                     ptr(nearer) if nearer.shape[0] else None, nearer.shape[0], image_size, mask_size,
                                     float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]), float(std[2]),
                                     ptr(work), ptr(images), ptr(masks), ptr(ignores), stream()))
+    return images, masks, ignores
+
+
+TRAIN_ID_ITEM_INTS, TRAIN_ID_COLS = 8, 8   # one row of sdn_train_id_stats' item table, one row of its output
+TRAIN_MIXED_ITEM_INTS = 32                 # one row of sdn_train_crops_mixed's item table
+
+
+def train_id_stats(items, max_pixels):
+    """The statistics of B (frame, id) items over several frames in one call (sdn_train_id_stats; derender3d/datasets.py:938-955
+    per object on the host): items int32 [B, 8] CUDA rows (address of the int32 [H, W] id map as two ints, address of the int32
+    [H, W] disparity map or 0, H, W, id, unused) -- derender3d.train_items.id_item_table --, max_pixels the largest H W among
+    them.  Returns table int32 [B, 8] CUDA rows (area, y0, x0, y1, x1, n, lo, hi) as scene_id_stats' rows; an absent id has
+    area 0 and the roi (INT_MAX, INT_MAX, 0, 0).  The maps the rows name must stay alive until the call has run.  Nothing is
+    copied to the host."""
+    items = want(items, torch.int32, 'items')
+    if items.dim() != 2 or items.shape[1] != TRAIN_ID_ITEM_INTS or items.shape[0] < 1:
+        raise ValueError('items must be int32 [B, %d] with B >= 1, got %s' % (TRAIN_ID_ITEM_INTS, tuple(items.shape)))
+    B = items.shape[0]
+    dev = items.device
+    with torch.cuda.device(dev):
+        table = torch.empty(B, TRAIN_ID_COLS, dtype=torch.int32, device=dev)
+        workspace = train_id_workspace(B, dev)
+        check(lib().sdn_train_id_stats(ptr(items), B, int(max_pixels), ptr(table), ptr(workspace), stream()))
+    return table
+
+
+def train_crops_mixed(rois_host, objs_host, items_host, tables, items, nearer, image_size=224, mask_size=256, maps=True):
+    """The crops of B training items whose frames, normalisations, mask and ignore sources differ per item
+    (sdn_train_crops_mixed; derender3d/datasets.py:141-172 as the KITTI, Cityscapes and VKitti classes call them), bit for bit
+    with sdn_train_crops.  rois_host numpy int32 [B, 4]; objs_host numpy int32 [B, 12] and tables = (objs, bounds, kk8) its CUDA
+    copy with Pillow's tables, made with each item's own frame size (derender3d.scene.crop_tables with one H and W per roi); items_host numpy
+    int32 [B, 32] and items its CUDA copy (derender3d.train_items.mixed_item_table; include/sdn_hip.h lists the row); nearer
+    uint8 [total, 3] CUDA (may be empty).  maps False: a batch without masks and ignores.  The tensors the rows name must stay
+    alive until the call has run.  Returns (images [B,3,S_i,S_i], masks [B,1,S_m,S_m] | None, ignores | None)."""
+    rois_host = np.ascontiguousarray(rois_host, dtype=np.int32)
+    objs_host = np.ascontiguousarray(objs_host, dtype=np.int32)
+    items_host = np.ascontiguousarray(items_host, dtype=np.int32)
+    if rois_host.ndim != 2 or rois_host.shape[1] != 4 or rois_host.shape[0] < 1:
+        raise ValueError('rois must be [B, 4] with B >= 1, got %s' % (rois_host.shape,))
+    B = rois_host.shape[0]
+    if objs_host.shape != (B, 12) or items_host.shape != (B, TRAIN_MIXED_ITEM_INTS):
+        raise ValueError('objs_host must be [%d, 12] and items_host [%d, %d], got %s, %s'
+                         % (B, B, TRAIN_MIXED_ITEM_INTS, objs_host.shape, items_host.shape))
+    objs, bounds, kk8 = (want(t, torch.int32, name) for t, name in zip(tables, ('objs', 'bounds', 'kk8')))
+    items = want(items, torch.int32, 'items')
+    nearer = want(nearer, torch.uint8, 'nearer')
+    if tuple(objs.shape) != (B, 12) or tuple(items.shape) != (B, TRAIN_MIXED_ITEM_INTS):
+        raise ValueError('objs must be [%d, 12] and items [%d, %d], got %s, %s'
+                         % (B, B, TRAIN_MIXED_ITEM_INTS, tuple(objs.shape), tuple(items.shape)))
+    if bounds.dim() != 2 or bounds.shape[1] != 2 or kk8.dim() != 1:
+        raise ValueError('bounds must be [M, 2] and kk8 [K], got %s, %s' % (tuple(bounds.shape), tuple(kk8.shape)))
+    if nearer.dim() != 2 or nearer.shape[1] != 3:
+        raise ValueError('nearer must be uint8 [total, 3], got %s' % (tuple(nearer.shape),))
+    dev = items.device
+    for t, name in ((objs, 'objs'), (bounds, 'bounds'), (kk8, 'kk8'), (nearer, 'nearer')):
+        if t.device != dev:
+            raise ValueError('%s is on %s, items on %s' % (name, t.device, dev))
+    with torch.cuda.device(dev):
+        images = torch.empty(B, 3, image_size, image_size, device=dev)
+        masks = torch.empty(B, 1, mask_size, mask_size, device=dev) if maps else None
+        ignores = torch.empty(B, 1, mask_size, mask_size, device=dev) if maps else None
+        work = torch.empty(B, dtype=torch.int64, device=dev)
+        check(lib().sdn_train_crops_mixed(rois_host.ctypes.data, objs_host.ctypes.data, ptr(objs), items_host.ctypes.data, ptr(items),
+                                          B, ptr(bounds), bounds.shape[0], ptr(kk8), kk8.shape[0],
+                                          ptr(nearer) if nearer.shape[0] else None, nearer.shape[0], image_size, mask_size,
+                                          ptr(work), ptr(images), ptr(masks), ptr(ignores), stream()))
     return images, masks, ignores

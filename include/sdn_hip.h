@@ -72,10 +72,10 @@ const char* sdn_last_error(void);
  * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
- * added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 16
+#define SDN_ABI_VERSION 17
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -704,6 +704,53 @@ int sdn_train_crops(const uint8_t* frames, const uint8_t* scenes, int Fr, int H,
                     const int32_t* bounds, int n_bounds, const int32_t* kk8, int n_kk8, const uint8_t* nearer, int n_nearer,
                     int image_size, int mask_size, float mean0, float mean1, float mean2, float std0, float std1, float std2,
                     void* workspace, float* images, float* masks, float* ignores, sdnStream stream);
+
+/* ---- the training items of the real-image sets and of the hybrid batches: geometric/derender3d/datasets.py:549-606
+ * (KittiObject.__getitem__), :737-769 (KittiSemantics), :930-971 (CityscapesSemantics), :1077-1112 (CityscapesMaskRCNN), mixed
+ * with :332-420 (VKitti) by HybridDataset (:175-190) and data_loader.py:17-37 (collate_fn) ------------------------------------
+ * sdn_train_id_stats (datasets.py:938-955 with :95-103 mask_to_roi, per object on the host: a full-frame comparison, a gather, a
+ * sort inside np.percentile): for B items over several frames in one call.  items: DEVICE int32 [B, 8] rows, aligned to 8 bytes
+ * (address of the item's int32 [H, W] id map as two ints, low word first; address of its int32 [H, W] disparity map, or 0; H; W;
+ * the id; one unused int).  Frames may differ in size, several items may name one frame.  max_pixels: the largest H W among the
+ * items (it sizes the launch; a larger frame is still walked completely).  table: DEVICE int32 [B, 8] rows (area, y0, x0, y1,
+ * x1, n, lo, hi) with the meaning of sdn_scene_id_stats' rows: the pixel count of ids == id, mask_to_roi's box, the number n of
+ * non-zero disparities under the mask, and their order statistics of zero-based rank floor(0.95 (n - 1)) and min(that + 1,
+ * n - 1) -- what np.percentile(., 95) interpolates between (derender3d.scene.percentile95_threshold); both 0 when n == 0 or
+ * when there is no disparity map.  An id that matches no pixel leaves area 0 and the roi (INT_MAX, INT_MAX, 0, 0).  An exact
+ * two-level radix select on the 16-bit values, per item: LDS histograms per workgroup, integer atomics only (the result does
+ * not depend on scheduling); the call clears table and workspace itself; nothing is copied to the host.  Disparities lie in
+ * 0 .. 65535; verified only with SDN_DEBUG_CHECKS=1 in the environment, which makes the call synchronous.  workspace: DEVICE,
+ * sdn_train_id_stats_workspace_bytes(B) bytes aligned to 16.  The rows of `items` are trusted: an address or a size that does
+ * not describe a live map reads out of bounds.
+ *
+ * sdn_train_crops_mixed (datasets.py:141-172 as called from :572-577, :764-767, :960-962, :1103-1110 and :415-417): the images
+ * [B, 3, image_size, image_size], masks and ignores [B, 1, mask_size, mask_size] of B items in one launch, after a statistics
+ * launch when an item's jitter holds contrast.  Window, padding quirk, fill values (127 / 0 / 255), Pillow's bilinear resize,
+ * to_tensor and the three fp32 operations of Normalize are those of sdn_train_crops, bit for bit.  rois_host, objs_host / objs,
+ * bounds, kk8, nearer and workspace as there, the object table made with each item's OWN frame size.  items / items_host: DEVICE
+ * (aligned to 8 bytes) and HOST int32 [B, 32] rows:
+ *   0-1    address of the item's uint8 [3, H, W] frame (two ints, low word first)
+ *   2-3    address of the mask source      4-5  address of the ignore source
+ *   6, 7   H, W of the item's frame
+ *   8      mask source: 0 none (the plane is 0.0), 1 colour code on a uint8 [H, W, 3] image, 2 id == on an int32 [H, W] map
+ *   9      the code r | g << 8 | b << 16, or the id
+ *   10     ignore source: 0 the plane is 0.0 everywhere, with no fill value (torch.zeros(1, 256, 256) of :767 and :1110, and
+ *          collate's zero fill); 1 the count of the item's nearer codes on a uint8 [H, W, 3] image, exactly as sdn_train_crops;
+ *          2 disparity > thr on an int32 [H, W] map, bytes 0 / 255, outside the frame 255
+ *   11     thr        12, 13  first row and number of rows of the item's codes in `nearer`
+ *   14-19  the colour jitter: number of ops, the ops in order, the three factors as fp32 bits, the hue shift (sdn_train_crops)
+ *   20-22  mean as fp32 bits    23-25  std as fp32 bits    26-31 unused
+ * masks and ignores may both be null (a batch without either; every item's sources must then be 0).  The validation of
+ * sdn_train_crops applies per item, on the HOST tables before any launch; in addition SDN_EINVAL for a null address that the
+ * item's sources need, a source kind outside the lists above, an int32 map that is not aligned to 4 bytes, a frame size below
+ * 1 or above INT_MAX / 4 pixels, a std of 0.  The validator is csrc/train_hybrid_check.h (tools/train_hybrid_check.cpp walks
+ * it on the CPU).  No float atomics, no host round trip: the outputs are identical from run to run. */
+int sdn_train_id_stats_workspace_bytes(int B, size_t* bytes);
+int sdn_train_id_stats(const int32_t* items, int B, long max_pixels, int32_t* table, void* workspace, sdnStream stream);
+int sdn_train_crops_mixed(const int32_t* rois_host, const int32_t* objs_host, const int32_t* objs, const int32_t* items_host,
+                          const int32_t* items, int B, const int32_t* bounds, int n_bounds, const int32_t* kk8, int n_kk8,
+                          const uint8_t* nearer, int n_nearer, int image_size, int mask_size, void* workspace, float* images,
+                          float* masks, float* ignores, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
