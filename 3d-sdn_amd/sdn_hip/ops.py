@@ -1406,3 +1406,87 @@ def train_crops_mixed(rois_host, objs_host, items_host, tables, items, nearer, i
                                           ptr(nearer) if nearer.shape[0] else None, nearer.shape[0], image_size, mask_size,
                                           ptr(work), ptr(images), ptr(masks), ptr(ignores), stream()))
     return images, masks, ignores
+
+
+SEGM_MAX_SCALES, SEGM_MAX_CLASSES, SEGM_MAX_COLORS, SEGM_UNKNOWN = 8, 32, 1024, -32768   # csrc/segm_tail_check.h
+
+
+def segm_scale_table(scores):
+    """The HOST table of sdn_segm_fuse for a list of fp32 [B, C, h_s, w_s] CUDA maps: numpy int32 [S, 4] rows (address as two
+    ints, low word first; h_s; w_s)."""
+    rows = np.zeros((len(scores), 2), dtype=np.uint64)
+    for s, t in enumerate(scores):
+        rows[s, 0] = t.data_ptr()
+        rows[s, 1] = (int(t.shape[3]) << 32) | int(t.shape[2])
+    return rows.view(np.int32).reshape(len(scores), 4)
+
+
+def segm_fuse(scores, H, W, probs=False):
+    """Multi-scale fusion of class scores to a label map (sdn_segm_fuse; semantic/vkitti_test.py:58-72 with models.py:401-402:
+    upsample, softmax, average over the scales on the device, torch.max on the host).  scores: a list of S fp32 [B, C, h_s, w_s]
+    CUDA tensors, one per test scale, the decoder's scores BEFORE upsample and softmax.  Returns labels uint8 [B, 1, H, W] --
+    what textural.edit.EditSession and textural.data.assemble take -- and, with probs, also the averaged probabilities fp32
+    [B, C, H, W].  Nothing is copied to the host."""
+    scores = [want(t, torch.float32, 'scores[%d]' % s) for s, t in enumerate(scores)]
+    if not scores:
+        raise ValueError('scores is empty')
+    if any(t.dim() != 4 for t in scores):
+        raise ValueError('every score map must be [B, C, h, w], got %s' % ([tuple(t.shape) for t in scores],))
+    B, C = scores[0].shape[:2]
+    dev = scores[0].device
+    for s, t in enumerate(scores):
+        if t.shape[0] != B or t.shape[1] != C or t.device != dev:
+            raise ValueError('scores[%d] is %s on %s, scores[0] %s on %s' % (s, tuple(t.shape), t.device, tuple(scores[0].shape), dev))
+    table = segm_scale_table(scores)
+    with torch.cuda.device(dev):
+        labels = torch.empty(B, 1, H, W, dtype=torch.uint8, device=dev)
+        pred = torch.empty(B, C, H, W, device=dev) if probs else None
+        check(lib().sdn_segm_fuse(table.ctypes.data, len(scores), B, C, int(H), int(W), ptr(labels), ptr(pred), stream()))
+    return (labels, pred) if probs else labels
+
+
+def segm_labels_from_colors(scene_u8, table_host, table):
+    """Ground-truth labels of a semantic colour image (sdn_segm_labels_from_colors; semantic/vkitti_dataset.py:206-209, 238: a
+    dictionary look-up per pixel through np.apply_along_axis).  scene_u8 uint8 [B, H, W, 3] CUDA; table_host numpy int32 [2 K]
+    (K ascending codes r | g << 8 | b << 16, then their labels) and table its CUDA copy -- semantic.segm_tail.color_table.
+    Returns (labels_gt int16 [B, H, W] = label - 1, unknown int32 [B]: the pixels per frame whose colour is not in the table,
+    which got -32768).  Nothing is copied to the host."""
+    scene_u8 = want(scene_u8, torch.uint8, 'scene_u8')
+    table = want(table, torch.int32, 'table')
+    table_host = np.ascontiguousarray(table_host, dtype=np.int32)
+    if scene_u8.dim() != 4 or scene_u8.shape[3] != 3:
+        raise ValueError('scene_u8 must be uint8 [B, H, W, 3], got %s' % (tuple(scene_u8.shape),))
+    if table_host.ndim != 1 or table_host.size % 2 or table_host.size < 2 or tuple(table.shape) != table_host.shape:
+        raise ValueError('table_host and table must be int32 [2 K] with K >= 1, got %s, %s' % (table_host.shape, tuple(table.shape)))
+    if table.device != scene_u8.device:
+        raise ValueError('table is on %s, scene_u8 on %s' % (table.device, scene_u8.device))
+    B, H, W = scene_u8.shape[:3]
+    dev = scene_u8.device
+    with torch.cuda.device(dev):
+        labels_gt = torch.empty(B, H, W, dtype=torch.int16, device=dev)
+        unknown = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib().sdn_segm_labels_from_colors(ptr(scene_u8), B, H, W, table_host.ctypes.data, ptr(table), table_host.size // 2,
+                                                ptr(labels_gt), ptr(unknown), stream()))
+    return labels_gt, unknown
+
+
+def segm_confusion(labels, labels_gt, num_class):
+    """The integers of accuracy() and intersectionAndUnion() (sdn_segm_confusion; semantic/utils.py:101-129 in numpy per
+    frame).  labels uint8 [B, 1, H, W] CUDA, labels_gt int16 [B, H, W] CUDA.  Returns counts int64 [B, 3 C + 3]:
+    area_intersection[C], area_pred[C], area_lab[C], acc_sum, valid_sum, the number of unknown-colour pixels.  Nothing is
+    copied to the host."""
+    labels = want(labels, torch.uint8, 'labels')
+    labels_gt = want(labels_gt, torch.int16, 'labels_gt')
+    if labels.dim() != 4 or labels.shape[1] != 1:
+        raise ValueError('labels must be uint8 [B, 1, H, W], got %s' % (tuple(labels.shape),))
+    B, _, H, W = labels.shape
+    if tuple(labels_gt.shape) != (B, H, W):
+        raise ValueError('labels_gt must be int16 [%d, %d, %d], got %s' % (B, H, W, tuple(labels_gt.shape)))
+    if labels_gt.device != labels.device:
+        raise ValueError('labels_gt is on %s, labels on %s' % (labels_gt.device, labels.device))
+    C = int(num_class)
+    dev = labels.device
+    with torch.cuda.device(dev):
+        counts = torch.empty(B, 3 * C + 3, dtype=torch.int64, device=dev)
+        check(lib().sdn_segm_confusion(ptr(labels), ptr(labels_gt), B, H, W, C, ptr(counts), stream()))
+    return counts

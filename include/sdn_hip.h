@@ -72,10 +72,11 @@ const char* sdn_last_error(void);
  * sdn_scene_edit added; 11: sdn_unmold_masks, sdn_scene_gt_masks added, timing slot 6; 12: sdn_scene_paint2d added; 13:
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
- * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
+ * sdn_segm_labels_from_colors, sdn_segm_confusion added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 17
+#define SDN_ABI_VERSION 18
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -751,6 +752,44 @@ int sdn_train_crops_mixed(const int32_t* rois_host, const int32_t* objs_host, co
                           const int32_t* items, int B, const int32_t* bounds, int n_bounds, const int32_t* kk8, int n_kk8,
                           const uint8_t* nearer, int n_nearer, int image_size, int mask_size, void* workspace, float* images,
                           float* masks, float* ignores, sdnStream stream);
+
+/* ---- the semantic tail: semantic/vkitti_test.py:56-73, vkitti_eval.py:64-107, models.py:401-402, utils.py:101-129,
+ * vkitti_dataset.py:206-209, 238 ---------------------------------------------------------------------------------------------
+ * The reference upsamples the decoder's scores of every test scale to the frame (nn.functional.upsample, bilinear,
+ * align_corners=False), takes the softmax there, averages the S full-resolution tensors, copies the sum to the host and takes
+ * torch.max on the CPU; its evaluation runs accuracy() and intersectionAndUnion() in numpy per frame on a ground-truth map
+ * built by a Python call per pixel.
+ *
+ * sdn_segm_fuse (vkitti_test.py:58-72, models.py:401-402): labels uint8 [B, 1, H, W] = arg-max over the classes of
+ * sum_s softmax_c(upsample(scores_s))[c] / S, in one launch, no full-resolution intermediate.  table_host: HOST int32 [S, 4]
+ * rows (address of the fp32 [B, C, h_s, w_s] DEVICE map as two ints, low word first; h_s; w_s); it travels as the kernel's
+ * argument, no copy of its own.  Per output pixel and scale: src = max(0, (dst + 0.5) * (h_s / H) - 0.5) with a float quotient,
+ * taps int(src) and the next row clamped to h_s - 1, columns alike; the four taps interpolated in fp32 for all C classes
+ * (l0y * (l0x a + l1x b) + l1y * (l0x c + l1x d), no FMA); softmax with the maximum subtracted and expf; p / S added in scale
+ * order.  The lowest class wins an exact tie, as torch.max on the CPU; a NaN among a pixel's inputs makes all its sums NaN and
+ * its label 0.  pred: fp32 [B, C, H, W], the sums, or NULL (the hot path).  1 <= S <= 8, 1 <= C <= 32, 1 <= B <= 65535,
+ * H, W, h_s, w_s <= 16384, h_s <= 2 H and w_s <= 2 W (a map may be larger than the output, up to twice); SDN_EINVAL otherwise
+ * and for a null or misaligned address.  No atomics: identical from run to run.  The tile, its LDS arithmetic and the validator
+ * are csrc/segm_tail_check.h (tools/segm_tail_check.cpp walks them on the CPU).
+ *
+ * sdn_segm_labels_from_colors (vkitti_dataset.py:206-209, 238): labels_gt int16 [B, H, W] = table label of the pixel's colour
+ * - 1 (unlabelled is -1) for scene uint8 [B, H, W, 3], the layout of sdn_scene_gt_masks.  table / table_host: DEVICE and HOST
+ * int32 [2 K]: the K codes r | g << 8 | b << 16 in strictly ascending order, then their K labels (0 .. 255, the reference's
+ * astype(np.uint8)); 1 <= K <= 1024; validated on the HOST copy.  A colour that is not in the table (the reference raises
+ * KeyError) gets -32768 and is counted: unknown int32 [B], cleared by the call.  scene, table and unknown aligned to 4 bytes,
+ * labels_gt to 8.
+ *
+ * sdn_segm_confusion (utils.py:101-129): counts int64 [B, 3 C + 3] per frame: area_intersection[C], area_pred[C], area_lab[C],
+ * acc_sum, valid_sum, the number of pixels with labels_gt == -32768; for labels uint8 [B, 1, H, W] and labels_gt int16
+ * [B, H, W].  The reference's masking: valid = labels_gt >= 0; the prediction counts only where valid; a label >= C falls out of
+ * the histograms (np.histogram(., bins=C, range=(1, C)) of label + 1) and still counts as valid -- and as wrong unless the
+ * prediction equals it -- in accuracy().  1 <= C <= 256.  Integer atomics only: exact, whatever the order.  The call clears
+ * counts and writes nothing outside it. */
+int sdn_segm_fuse(const int32_t* table_host, int S, int B, int C, int H, int W, uint8_t* labels, float* pred, sdnStream stream);
+int sdn_segm_labels_from_colors(const uint8_t* scene, int B, int H, int W, const int32_t* table_host, const int32_t* table, int K,
+                                int16_t* labels_gt, int32_t* unknown, sdnStream stream);
+int sdn_segm_confusion(const uint8_t* labels, const int16_t* labels_gt, int B, int H, int W, int C, int64_t* counts,
+                       sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
