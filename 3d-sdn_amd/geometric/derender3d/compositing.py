@@ -22,45 +22,7 @@ import os
 import numpy as np
 import torch
 
-PRECISION_BITS = 32 - 8 - 2  # Pillow, Resample.c
-
-
-@functools.lru_cache(maxsize=256)
-def resample_tables(in_size, out_size):
-    """Pillow's precompute_coeffs for the bilinear filter (support 1.0), box = the whole image.
-    Returns (ksize, bounds int32 [out, 2] = (first source index, count), kk float64 [out, ksize]); cached per size pair
-    (treat the arrays as read-only)."""
-    scale = np.float64(np.float32(in_size) - np.float32(0.0)) / out_size
-    filterscale = max(scale, 1.0)
-    support = 1.0 * filterscale
-    ksize = int(np.ceil(support)) * 2 + 1
-    xx = np.arange(out_size, dtype=np.float64)
-    center = 0.0 + (xx + 0.5) * scale
-    ss = 1.0 / filterscale
-    xmin = (center - support + 0.5).astype(np.int64)   # C cast: truncation (the operands are > -1 here)
-    xmin = np.maximum(xmin, 0)
-    xmax = (center + support + 0.5).astype(np.int64)
-    xmax = np.minimum(xmax, in_size)
-    cnt = xmax - xmin
-    kk = np.zeros((out_size, ksize), dtype=np.float64)
-    ww = np.zeros(out_size, dtype=np.float64)
-    for x in range(ksize):
-        arg = (x + xmin - center + 0.5) * ss
-        arg = np.where(arg < 0.0, -arg, arg)
-        w = np.where(arg < 1.0, 1.0 - arg, 0.0)
-        w = np.where(x < cnt, w, 0.0)
-        kk[:, x] = w
-        ww = ww + w          # same order as the C loop
-    nz = ww != 0.0
-    kk[nz] = kk[nz] / ww[nz, None]
-    bounds = np.stack([xmin, cnt], axis=1).astype(np.int32)
-    return ksize, bounds, kk
-
-
-def fixed_point(kk):
-    """normalize_coeffs_8bpc: (int)(+-0.5 + k * 2^22), C truncation."""
-    v = kk * float(1 << PRECISION_BITS)
-    return np.where(kk < 0, np.trunc(-0.5 + v), np.trunc(0.5 + v)).astype(np.int32)
+from sdn_hip.pillow import PRECISION_BITS, fixed_point, resample_tables  # noqa: E402,F401  (moved there: the semantic branch shares them)
 
 
 def resample_u8_numpy(img, out_size):

@@ -33,9 +33,9 @@ import torch
 
 from derender3d import TargetType
 from derender3d import scene as _scene
+from sdn_hip.pillow import BRIGHTNESS, CONTRAST, HUE, SATURATION, jitter_params  # noqa: F401  (moved there: the semantic branch shares them)
 
 ITEM_INTS = 12     # one row of sdn_train_crops's item table
-BRIGHTNESS, CONTRAST, SATURATION, HUE = 0, 1, 2, 3
 
 TARGET_KEYS = ('rois', 'roi_norms', 'thetas', 'rotations', 'translations', 'translation2ds', 'scales', 'log_scales', 'log_depths',
                'widths', 'heights', 'focals', 'u0s', 'v0s')
@@ -60,32 +60,6 @@ def roi_jitter(roi, ratio=0.1, rng=random):
     right) moves by one rng.randint, the rows within +- int(ratio * height), the columns within +- int(ratio * width)."""
     reach = (int(ratio * (roi[2] - roi[0])), int(ratio * (roi[3] - roi[1])))       # (rows, columns)
     return [int(edge) + rng.randint(-reach[k % 2], reach[k % 2]) for k, edge in enumerate(roi)]
-
-
-def jitter_params(brightness=.5, contrast=.5, saturation=.5, hue=.5, rng=random):
-    """The draws of torchvision 0.2.1's ColorJitter.get_params -> (order, factors, hue_shift): `order` the ops present
-    (BRIGHTNESS, CONTRAST, SATURATION, HUE) as shuffled, `factors` the brightness, contrast and saturation factors (1.0 for an
-    absent op), `hue_shift` what adjust_hue adds to the H plane: int(hue_factor * 255) % 256, C's truncation toward zero and the
-    wrap of np.uint8(...).  One uniform draw per present op in the order brightness, contrast, saturation, hue, then one shuffle
-    of the list of ops.
-
-    torchvision is not among this project's dependencies: the SAMPLING here is a restatement and is not pinned against it.
-    Only the APPLICATION of given parameters (sdn_train_crops) is pinned, against Pillow."""
-    order, factors, hue_shift = [], [1.0, 1.0, 1.0], 0
-    if brightness > 0:
-        factors[0] = rng.uniform(max(0, 1 - brightness), 1 + brightness)
-        order.append(BRIGHTNESS)
-    if contrast > 0:
-        factors[1] = rng.uniform(max(0, 1 - contrast), 1 + contrast)
-        order.append(CONTRAST)
-    if saturation > 0:
-        factors[2] = rng.uniform(max(0, 1 - saturation), 1 + saturation)
-        order.append(SATURATION)
-    if hue > 0:
-        hue_shift = int(rng.uniform(-hue, hue) * 255) % 256
-        order.append(HUE)
-    rng.shuffle(order)
-    return order, tuple(factors), hue_shift
 
 
 def squared_distances(x3d, y3d, h3d, z3d):

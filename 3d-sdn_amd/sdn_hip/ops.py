@@ -1490,3 +1490,41 @@ def segm_confusion(labels, labels_gt, num_class):
         counts = torch.empty(B, 3 * C + 3, dtype=torch.int64, device=dev)
         check(lib().sdn_segm_confusion(ptr(labels), ptr(labels_gt), B, H, W, C, ptr(counts), stream()))
     return counts
+
+
+SEGM_TRAIN_ITEM_INTS, SEGM_TRAIN_STAT_PIXELS = 20, 2048   # csrc/segm_train_check.h: SGT_ITEM_INTS, SGT_STAT_PIXELS
+
+
+def segm_train_batch(frames_u8, scenes_u8, tables_host, Hb, Wb, rate, mean, std):
+    """One training batch of the semantic branch (sdn_segm_train_batch; semantic/vkitti_dataset.py:111-159 per item on the
+    host): colour jitter, flip, Pillow's BILINEAR resize, BGR + Normalize and the zero padding for the images, the two NEAREST
+    resizes composed into one gather for the labels.  frames_u8, scenes_u8 uint8 [B, H, W, 3] CUDA; tables_host numpy int32 [n]:
+    the B item rows of 20 ints and every table they name (semantic.train_items.table_buffer; include/sdn_hip.h lists the row).
+    It is uploaded here, in one copy.  Returns (img_data fp32 [B, 3, Hb, Wb], seg_label int64 [B, Hb // rate, Wb // rate],
+    unknown int32 [B]).  Nothing is copied to the host."""
+    frames_u8 = want(frames_u8, torch.uint8, 'frames_u8')
+    scenes_u8 = want(scenes_u8, torch.uint8, 'scenes_u8')
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError('frames_u8 must be uint8 [B, H, W, 3], got %s' % (tuple(frames_u8.shape),))
+    B, H, W, _ = frames_u8.shape
+    if tuple(scenes_u8.shape) != (B, H, W, 3):
+        raise ValueError('scenes_u8 must be uint8 [%d, %d, %d, 3], got %s' % (B, H, W, tuple(scenes_u8.shape)))
+    dev = frames_u8.device
+    if scenes_u8.device != dev:
+        raise ValueError('scenes_u8 is on %s, frames_u8 on %s' % (scenes_u8.device, dev))
+    tables_host = np.ascontiguousarray(tables_host, dtype=np.int32)
+    if tables_host.ndim != 1 or tables_host.size < B * SEGM_TRAIN_ITEM_INTS:
+        raise ValueError('tables_host must be int32 [n] with n >= %d, got %s' % (B * SEGM_TRAIN_ITEM_INTS, tables_host.shape))
+    Hb, Wb, rate = int(Hb), int(Wb), int(rate)
+    if Hb < 1 or Wb < 1 or rate < 1 or rate > Hb or rate > Wb:
+        raise ValueError('bad batch sizes: %d x %d at label rate %d' % (Hb, Wb, rate))
+    with torch.cuda.device(dev):
+        tables = torch.from_numpy(tables_host).to(dev)   # the one upload
+        work = torch.empty(B * (-(-H * W // SEGM_TRAIN_STAT_PIXELS)), dtype=torch.int32, device=dev)
+        img = torch.empty(B, 3, Hb, Wb, device=dev)
+        lab = torch.empty(B, Hb // rate, Wb // rate, dtype=torch.int64, device=dev)
+        unknown = torch.empty(B, dtype=torch.int32, device=dev)
+        check(lib().sdn_segm_train_batch(ptr(frames_u8), ptr(scenes_u8), B, H, W, tables_host.ctypes.data, ptr(tables), tables_host.size,
+                                         Hb, Wb, rate, float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]),
+                                         float(std[2]), ptr(work), work.numel(), ptr(img), ptr(lab), ptr(unknown), stream()))
+    return img, lab, unknown

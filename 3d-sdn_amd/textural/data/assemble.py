@@ -23,6 +23,8 @@ from math import cos, pi, sin
 import numpy as np
 import torch
 
+from sdn_hip import pillow as _pillow
+
 PRECISION_BITS = 32 - 8 - 2  # Pillow, Resample.c
 
 
@@ -72,14 +74,8 @@ def _resample_table(in_size, out_size, method):
 
 @functools.lru_cache(maxsize=64)
 def _nearest_table(in_size, out_size):
-    """Pillow ImagingScaleAffine: the source index of output x is (int) of xo, xo = a/2, a/2 + a, ... summed in double."""
-    a = np.float64(in_size) / out_size
-    xo = a * 0.5
-    idx = np.zeros(out_size, dtype=np.int64)
-    for x in range(out_size):
-        idx[x] = int(xo)
-        xo += a
-    return torch.from_numpy(np.minimum(idx, in_size - 1))
+    """Pillow's NEAREST source indices (sdn_hip.pillow.nearest_table) as a tensor."""
+    return torch.from_numpy(_pillow.nearest_table(in_size, out_size))
 
 
 _TABLES_ON = {}

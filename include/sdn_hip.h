@@ -73,10 +73,10 @@ const char* sdn_last_error(void);
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
  * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
- * sdn_segm_labels_from_colors, sdn_segm_confusion added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 18
+#define SDN_ABI_VERSION 19
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -790,6 +790,35 @@ int sdn_segm_labels_from_colors(const uint8_t* scene, int B, int H, int W, const
                                 int16_t* labels_gt, int32_t* unknown, sdnStream stream);
 int sdn_segm_confusion(const uint8_t* labels, const int16_t* labels_gt, int B, int H, int W, int C, int64_t* counts,
                        sdnStream stream);
+
+/* ---- the semantic training batch: semantic/vkitti_dataset.py:74-163 (TrainDataset.__getitem__) ------------------------------------
+ * The reference builds every item on the host: the label of every scene pixel by a Python call (:120), torchvision's ColorJitter
+ * through Pillow (:124), cv2.flip (:132-136), scipy.misc.imresize three times (:139-150), RGB to BGR and Normalize (:152-154),
+ * and the copy into the zero batch tensors (:107-109, :156-159).  sdn_segm_train_batch does :120-159 for B items in at most
+ * three launches (the luma sums of the contrast op, only when an item has one; the images; the labels), bit for bit with Pillow:
+ *   img_data fp32 [B, 3, Hb, Wb]: per item the frame after the jitter ops in the item's order (Pillow's arithmetic as
+ *     sdn_train_crops applies it; the contrast grey is int(mean(L) + 0.5) over the WHOLE frame), mirrored when flip is set,
+ *     resized to (h, w) by Pillow's BILINEAR resize (horizontal pass into bytes, then vertical, 22-bit coefficients; a pass whose
+ *     size does not change is skipped), then out[c, y, x] = ((float)px[y, x, 2 - c] - mean_c) / std_c in fp32 with a true
+ *     division: mean and std are indexed by the OUTPUT channel, so the reference's RGB constants meet the BGR planes (:152-154).
+ *     0 where y >= h or x >= w.  Every element is written.
+ *   seg_label int64 [B, Hb / rate, Wb / rate]: the NEAREST resize to (h, w), the zero padding to multiples of rate and the
+ *     NEAREST resize by exactly rate (:140-150) composed: table label of scene[yn[rate y + rate / 2], flip(xn[rate x + rate / 2])]
+ *     - 1 where rate y + rate / 2 < h and rate x + rate / 2 < w, -1 elsewhere (:159).  A colour that is not in the item's table
+ *     (the reference raises KeyError at :120) gives -1 and is counted in unknown int32 [B]; only SAMPLED pixels are looked up.
+ * frames, scenes: uint8 [B, H, W, 3] DEVICE.  tables / tables_host: DEVICE and HOST copies of ONE int32 buffer of n_tables ints, so
+ * that everything goes up in one copy: B item rows of 20 ints first (csrc/segm_train_check.h: h, w, flip, nops, order, the three
+ * factors as floats, hue shift, then offsets into the same buffer: horizontal bounds [w][2] and coefficients [w][ksize] with
+ * their ksize (0 for a skipped pass), the vertical ones, the NEAREST column and row tables, the colour table (K codes ascending,
+ * K labels) and K, one pad), then the tables the rows name.  Every entry is validated on the HOST copy before any launch:
+ * SDN_EINVAL for a bad row, a table outside the buffer, a bound outside the frame, contrast on a frame of more than 2^21 pixels,
+ * W > 4096, or an item whose band of 4 output rows needs more resampled source rows than the 12 KiB LDS plane holds (refused,
+ * never truncated).  workspace: int32 [n_workspace], at least B * ceil(H W / 2048) ints when an item has contrast.  No float
+ * atomics; the one integer atomic is the unknown count: identical from run to run. */
+int sdn_segm_train_batch(const uint8_t* frames, const uint8_t* scenes, int B, int H, int W, const int32_t* tables_host,
+                         const int32_t* tables, long n_tables, int Hb, int Wb, int rate, float mean0, float mean1, float mean2,
+                         float std0, float std1, float std2, int32_t* workspace, long n_workspace, float* img_data,
+                         int64_t* seg_label, int32_t* unknown, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
