@@ -18,7 +18,7 @@ LIB_PATH = os.path.normpath(os.path.join(_HERE, '..', 'lib', 'libsdn_hip.so'))
 RGB, ALPHA, DEPTH, AA, FACE_COLOR, SAVE_MAPS, ACCUMULATE, SERIAL_EDGES, STREAM_FACES, COUNT_WORK = 1, 2, 4, 8, 16, 32, 64, 128, 256, 512
 K1_COVERAGE = 4096   # SDN_K1_COVERAGE: the reference's default ("unsafe") forward kernel's coverage rule, deterministic ties
 
-ABI_VERSION = 19   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
+ABI_VERSION = 20   # include/sdn_hip.h: SDN_ABI_VERSION this binding was written against (buffer sizes, argument lists)
 
 _lib = None
 _lock = threading.Lock()
@@ -116,6 +116,8 @@ def _declare(L):
     sig['sdn_segm_labels_from_colors'] = [_vp, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp, _vp]
     sig['sdn_segm_confusion'] = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
     sig['sdn_segm_train_batch'] = [_vp, _vp, _ci, _ci, _ci, _vp, _vp, _cl, _ci, _ci, _ci] + [_cf] * 6 + [_vp, _cl, _vp, _vp, _vp, _vp]
+    sig['sdn_segm_loss_fwd'] = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _vp, _sz, _vp, _vp, _vp, _vp]
+    sig['sdn_segm_loss_bwd'] = [_vp, _vp, _vp, _ci, _ci, _ci, _ci, _cf, _vp, _vp, _vp, _vp, _vp, _vp]
     sig['sdn_train_losses_scratch'] = [_ci, _ci, _cl, ctypes.POINTER(_sz)]
     sig['sdn_train_losses_fwd'] = [_vp] * 7 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp]
     sig['sdn_train_losses_bwd'] = [_vp] * 6 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd] + [_vp] * 9 + [_vp]
@@ -193,7 +195,7 @@ def exported_symbols():
             'sdn_scene_id_workspace_bytes', 'sdn_scene_id_stats', 'sdn_scene_id_planes', 'sdn_assemble_planes', 'sdn_assemble_maps',
             'sdn_train_rois', 'sdn_train_crops', 'sdn_train_id_stats_workspace_bytes', 'sdn_train_id_stats', 'sdn_train_crops_mixed',
             'sdn_train_losses_scratch', 'sdn_train_losses_fwd', 'sdn_train_losses_bwd',
-            'sdn_segm_fuse', 'sdn_segm_labels_from_colors', 'sdn_segm_confusion', 'sdn_segm_train_batch',
+            'sdn_segm_fuse', 'sdn_segm_labels_from_colors', 'sdn_segm_confusion', 'sdn_segm_train_batch', 'sdn_segm_loss_fwd', 'sdn_segm_loss_bwd',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',

@@ -9,6 +9,7 @@ Each Function mirrors one piece of the reference's Chainer graph (paths under
 """
 import numpy as np
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, lib, ptr, raster_bwd_workspace,
                raster_workspace, scene_id_workspace, stream, train_id_workspace, want)
@@ -1528,3 +1529,77 @@ def segm_train_batch(frames_u8, scenes_u8, tables_host, Hb, Wb, rate, mean, std)
                                          Hb, Wb, rate, float(mean[0]), float(mean[1]), float(mean[2]), float(std[0]), float(std[1]),
                                          float(std[2]), ptr(work), work.numel(), ptr(img), ptr(lab), ptr(unknown), stream()))
     return img, lab, unknown
+
+
+SEGM_LOSS_PIXELS, SEGM_LOSS_PART_BYTES = 256, 32   # csrc/segm_loss_check.h: SGL_PIXELS, SGL_PART_BYTES
+
+
+class SegmLossFn(torch.autograd.Function):
+    """The training branch of SegmentationModule.forward after the network call (semantic/models.py:39-45 with pixel_acc,
+    :15-21, the decoders' log_softmax, :279-280, 412-413, and nn.NLLLoss(ignore_index=-1), vkitti_train.py:133) on the class
+    SCORES of both decoder heads -- sdn_segm_loss_fwd / _bwd (include/sdn_hip.h), forward in two launches, backward in one.
+    Returns (out fp32 [4]: loss, acc, loss_main, loss_deepsup; counts int64 [3]: acc_sum, pixel_sum, bad).  `segm_loss` below
+    checks types and shapes; a CPU tensor raises NotImplementedError here."""
+
+    @staticmethod
+    def forward(ctx, scores, scores_deepsup, seg_label, deep_sup_scale):
+        s0, s1, lab = _f32(scores, 'scores'), _f32(scores_deepsup, 'scores_deepsup'), want(seg_label, torch.int64, 'seg_label')
+        B, C, h, w = s0.shape
+        scale = float(deep_sup_scale) if s1 is not None else 0.0
+        dev = s0.device
+        with torch.cuda.device(dev):
+            scratch = torch.empty(B * (-(-h * w // SEGM_LOSS_PIXELS)) * SEGM_LOSS_PART_BYTES, dtype=torch.uint8, device=dev)
+            lse = torch.empty(2, B, h, w, dtype=torch.float32, device=dev)
+            out = torch.empty(4, dtype=torch.float32, device=dev)
+            counts = torch.empty(3, dtype=torch.int64, device=dev)
+            check(lib().sdn_segm_loss_fwd(ptr(s0), ptr(s1), ptr(lab), B, C, h, w, scale, ptr(scratch), scratch.numel(), ptr(lse), ptr(out),
+                                          ptr(counts), stream()))
+        ctx.save_for_backward(s0, s1, lab, lse, counts)
+        ctx.scale = scale
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, _g_counts):
+        s0, s1, lab, lse, counts = ctx.saved_tensors
+        need0 = ctx.needs_input_grad[0]
+        need1 = s1 is not None and ctx.needs_input_grad[1]
+        if not (need0 or need1):
+            return None, None, None, None
+        B, C, h, w = s0.shape
+        with torch.cuda.device(s0.device):
+            go = g_out.to(torch.float32).contiguous()
+            g0 = torch.empty_like(s0) if need0 else None
+            g1 = torch.empty_like(s1) if need1 else None
+            check(lib().sdn_segm_loss_bwd(ptr(s0), ptr(s1), ptr(lab), B, C, h, w, ctx.scale, ptr(lse), ptr(counts), ptr(go), ptr(g0),
+                                          ptr(g1), stream()))
+        return g0, g1, None, None
+
+
+def segm_loss(scores, scores_deepsup, seg_label, deep_sup_scale):
+    """(out fp32 [4] = loss, acc, loss_main, loss_deepsup; counts int64 [3] = acc_sum, pixel_sum, bad) of the semantic training
+    step for the decoder's class scores fp32 [B, C, h, w] (scores_deepsup: the same shape, or None), seg_label int64 [B, h, w]
+    (-1: ignored; any other label outside [0, C) is ignored too and counted in bad) and the Python float deep_sup_scale.
+    Differentiable in both score tensors; counts is not.  Nothing is copied to the host.  A wrong type or dtype raises
+    TypeError, a wrong shape ValueError, a CPU tensor NotImplementedError."""
+    for t, name, dtype in ((scores, 'scores', torch.float32), (scores_deepsup, 'scores_deepsup', torch.float32),
+                           (seg_label, 'seg_label', torch.int64)):
+        if t is None and name == 'scores_deepsup':
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+        if t.dtype != dtype:
+            raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
+    if scores.dim() != 4:
+        raise ValueError('scores must be fp32 [B, C, h, w], got %s' % (tuple(scores.shape),))
+    B, C, h, w = scores.shape
+    if C < 1 or C > SEGM_MAX_CLASSES or B < 1 or h < 1 or w < 1:
+        raise ValueError('scores is %s; 1 to %d classes and no empty axis are supported' % (tuple(scores.shape), SEGM_MAX_CLASSES))
+    if scores_deepsup is not None and (scores_deepsup.shape != scores.shape or scores_deepsup.device != scores.device):
+        raise ValueError('scores_deepsup is %s on %s, scores %s on %s' % (tuple(scores_deepsup.shape), scores_deepsup.device,
+                                                                        tuple(scores.shape), scores.device))
+    if tuple(seg_label.shape) != (B, h, w) or seg_label.device != scores.device:
+        raise ValueError('seg_label must be int64 [%d, %d, %d] on %s, got %s on %s' % (B, h, w, scores.device, tuple(seg_label.shape),
+                                                                                     seg_label.device))
+    return SegmLossFn.apply(scores, scores_deepsup, seg_label, 0.0 if deep_sup_scale is None else deep_sup_scale)

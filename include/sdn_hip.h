@@ -73,10 +73,11 @@ const char* sdn_last_error(void);
  * sdn_scene_id_workspace_bytes, sdn_scene_id_stats, sdn_scene_id_planes added; 14: sdn_assemble_planes, sdn_assemble_maps
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
  * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
- * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added; 20: sdn_segm_loss_fwd,
+ * sdn_segm_loss_bwd added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
-#define SDN_ABI_VERSION 19
+#define SDN_ABI_VERSION 20
 int sdn_version(void);
 
 /* ---- camera: neural_renderer/look.py:7-45, look_at.py:7-46, perspective.py:5-19 ------------------
@@ -819,6 +820,39 @@ int sdn_segm_train_batch(const uint8_t* frames, const uint8_t* scenes, int B, in
                          const int32_t* tables, long n_tables, int Hb, int Wb, int rate, float mean0, float mean1, float mean2,
                          float std0, float std1, float std2, int32_t* workspace, long n_workspace, float* img_data,
                          int64_t* seg_label, int32_t* unknown, sdnStream stream);
+
+/* ---- the semantic training loss: semantic/models.py:15-21, 39-45 (pixel_acc and the training branch of
+ * SegmentationModule.forward), the decoders' log_softmax (models.py:279-280, 412-413), nn.NLLLoss(ignore_index=-1)
+ * (vkitti_train.py:133) ------------------------------------------------------------------------------------------------------------
+ * The reference takes log_softmax of both decoder heads, applies NLLLoss to each, adds loss + loss_deepsup * deep_sup_scale and
+ * runs pixel_acc (torch.max, two .long() masks, two sums, a float division): about twenty small launches each way.
+ *
+ * sdn_segm_loss_fwd (models.py:39-45 with :15-21, :279-280, :412-413), two launches:
+ *   scores, scores_deepsup: fp32 [B, C, h, w] DEVICE, the outputs of decoder.conv_last / conv_last_deepsup BEFORE log_softmax;
+ *     scores_deepsup may be NULL (no deep supervision: loss = loss_main, loss_deepsup = 0).  seg_label: int64 [B, h, w], what
+ *     sdn_segm_train_batch writes.  A pixel is valid iff 0 <= label < C; -1 is the ignore label; any other label is ignored in the
+ *     loss and in the accuracy and counted in `bad` (the reference raises there).
+ *   out fp32 [4]: loss = loss_main + loss_deepsup * deep_sup_scale (fp32, :42), acc = float(acc_sum) / (float(pixel_sum) + 1e-10f)
+ *     in fp32 (:20; 0 without a valid pixel), loss_main and loss_deepsup = the sum over the valid pixels of -(x[label] - lse) /
+ *     pixel_sum, lse = max + log(sum exp(x - max)) per pixel in fp32, the sum in fp64 (0 / 0 = NaN without a valid pixel, as
+ *     NLLLoss gives).  counts int64 [3]: acc_sum, pixel_sum, bad.  The prediction of pixel_acc is the arg-max of the main head's
+ *     SCORES with a strict >: the lowest class wins an exact tie (torch.max on the CPU) and a NaN never wins (torch.max would
+ *     return the NaN's class); a NaN score makes lse and, on a valid pixel, the loss NaN.
+ *   lse fp32 [2, B, h, w]: both heads' lse for the backward call (zeros for an absent head).  scratch: scratch_bytes >= 32 *
+ *     B * ceil(h w / 256) bytes, aligned to 8 (csrc/segm_loss_check.h: SGL_PIXELS, SGL_PART_BYTES); nothing needs zeroing.
+ * sdn_segm_loss_bwd (the autograd of the above), one launch: grad_scores / grad_scores_deepsup fp32 [B, C, h, w], either may be
+ *   NULL; every element of a given one is written: (exp(x[c] - lse) - [c == label]) * g / pixel_sum on a valid pixel, 0 on an
+ *   ignored one, with g = grad_out[0] + grad_out[2] for the main head and grad_out[0] * deep_sup_scale + grad_out[3] for the
+ *   deepsup head (grad_out fp32 [4] DEVICE, the gradient of `out`; acc carries none); pixel_sum is read from counts on the device.
+ * 1 <= C <= 32, B, h, w >= 1, B * C * h * w < 2^31; SDN_EINVAL with a message otherwise and for a NULL pointer, before any launch.
+ * 16-byte loads across four adjacent pixels when h * w % 4 == 0 and every base is 16-byte aligned, scalar loads otherwise.  No
+ * atomics; identical from run to run; nothing crosses to the host. */
+int sdn_segm_loss_fwd(const float* scores, const float* scores_deepsup, const int64_t* seg_label, int B, int C, int h, int w,
+                      float deep_sup_scale, void* scratch, size_t scratch_bytes, float* lse, float* out, int64_t* counts,
+                      sdnStream stream);
+int sdn_segm_loss_bwd(const float* scores, const float* scores_deepsup, const int64_t* seg_label, int B, int C, int h, int w,
+                      float deep_sup_scale, const float* lse, const int64_t* counts, const float* grad_out, float* grad_scores,
+                      float* grad_scores_deepsup, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
