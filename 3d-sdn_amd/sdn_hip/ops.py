@@ -7,6 +7,8 @@ Each Function mirrors one piece of the reference's Chainer graph (paths under
   FaceNormals      normalize(cross(v10, v12))        derender3d/models/renderer.py:66-76
   RasterizeMaps    Rasterize + flip + 2x2 pool       neural_renderer/rasterize.py:19-974
 """
+import ctypes
+
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
@@ -1603,3 +1605,158 @@ def segm_loss(scores, scores_deepsup, seg_label, deep_sup_scale):
         raise ValueError('seg_label must be int64 [%d, %d, %d] on %s, got %s on %s' % (B, h, w, scores.device, tuple(seg_label.shape),
                                                                                      seg_label.device))
     return SegmLossFn.apply(scores, scores_deepsup, seg_label, 0.0 if deep_sup_scale is None else deep_sup_scale)
+
+
+SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
+
+
+def _ppm_ints(values):
+    return (ctypes.c_int * len(values))(*values)
+
+
+def _ppm_ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
+class SegmPpmPoolFn(torch.autograd.Function):
+    """First half of the pyramid pooling module (semantic/models.py:336-346, 387-397): sdn_segm_ppm_pool forward,
+    sdn_segm_ppm_pool_bwd backward, one launch each.  Returns (cat [B, C + sum K, h, w] with conv5 in its first C channels and
+    the others left for SegmPpmFillFn, p_1 .. p_S [B, C, s_k, s_k]: torch's AdaptiveAvgPool2d(s_k) of conv5, contiguous segments
+    of one buffer).  `segm_ppm_pool` below checks types and shapes."""
+
+    @staticmethod
+    def forward(ctx, conv5, scales, branch_channels):
+        x = _f32(conv5, 'conv5')
+        B, C, h, w = x.shape
+        dev = x.device
+        with torch.cuda.device(dev):
+            cat = torch.empty(B, C + sum(branch_channels), h, w, dtype=torch.float32, device=dev)
+            pooled = torch.empty(B * C * sum(s * s for s in scales), dtype=torch.float32, device=dev)
+            check(lib().sdn_segm_ppm_pool(ptr(x), B, C, h, w, _ppm_ints(scales), _ppm_ints(branch_channels), len(scales), ptr(cat),
+                                          ptr(pooled), stream()))
+        ps, at = [], 0
+        for s in scales:
+            ps.append(pooled[at:at + B * C * s * s].view(B, C, s, s))
+            at += B * C * s * s
+        ctx.scales, ctx.channels, ctx.shape = tuple(scales), tuple(branch_channels), (B, C, h, w)
+        ctx.set_materialize_grads(False)   # an unused output arrives as None, not as a tensor of zeros to be read
+        return (cat,) + tuple(ps)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_cat, *g_p):
+        if not ctx.needs_input_grad[0] or (g_cat is None and all(g is None for g in g_p)):
+            return None, None, None
+        B, C, h, w = ctx.shape
+        given = [g for g in (g_cat,) + tuple(g_p) if g is not None]
+        dev = given[0].device
+        with torch.cuda.device(dev):
+            g_cat = None if g_cat is None else g_cat.to(torch.float32).contiguous()
+            g_p = [None if g is None else g.to(torch.float32).contiguous() for g in g_p]
+            gx = torch.empty(B, C, h, w, dtype=torch.float32, device=dev)
+            check(lib().sdn_segm_ppm_pool_bwd(ptr(g_cat), _ppm_ptrs(g_p), B, C, h, w, _ppm_ints(ctx.scales), _ppm_ints(ctx.channels),
+                                              len(ctx.scales), ptr(gx), stream()))
+        return gx, None, None
+
+
+class SegmPpmFillFn(torch.autograd.Function):
+    """Second half of the pyramid pooling module: sdn_segm_ppm_fill writes the bilinear upsampling of the branch outputs y_k
+    [B, K_k, s_k, s_k] into the channels >= C of `cat`, IN PLACE (ctx.mark_dirty), and returns cat; sdn_segm_ppm_fill_bwd gives
+    the gradients of the y_k that need one, and the gradient of `cat` is the incoming one itself, uncopied -- SegmPpmPoolFn's
+    backward reads its first C channels."""
+
+    @staticmethod
+    def forward(ctx, cat, C, *ys):
+        ys = [_f32(y, 'y[%d]' % k) for k, y in enumerate(ys)]
+        B, _, h, w = cat.shape
+        scales, channels = [int(y.shape[2]) for y in ys], [int(y.shape[1]) for y in ys]
+        with torch.cuda.device(cat.device):
+            check(lib().sdn_segm_ppm_fill(_ppm_ptrs(ys), B, C, h, w, _ppm_ints(scales), _ppm_ints(channels), len(ys), ptr(cat), stream()))
+        ctx.mark_dirty(cat)
+        ctx.scales, ctx.channels, ctx.C = scales, channels, C
+        return cat
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        need = ctx.needs_input_grad[2:]
+        gys = [None] * len(need)
+        if any(need):
+            B, _, h, w = g.shape
+            with torch.cuda.device(g.device):
+                g = g.to(torch.float32).contiguous()
+                gys = [torch.empty(B, K, s, s, dtype=torch.float32, device=g.device) if n else None
+                       for n, K, s in zip(need, ctx.channels, ctx.scales)]
+                check(lib().sdn_segm_ppm_fill_bwd(ptr(g), B, ctx.C, h, w, _ppm_ints(ctx.scales), _ppm_ints(ctx.channels), len(need),
+                                                  _ppm_ptrs(gys), stream()))
+        return (g if ctx.needs_input_grad[0] else None, None) + tuple(gys)
+
+
+def _ppm_tensor(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if t.dtype != torch.float32:
+        raise TypeError('%s must be torch.float32, got %s' % (name, t.dtype))
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError('%s must be fp32 [B, C, h, w] without an empty axis, got %s' % (name, tuple(t.shape)))
+
+
+def segm_ppm_pool(conv5, scales, branch_channels):
+    """(cat, p_1 .. p_S) of SegmPpmPoolFn for conv5 CUDA fp32 [B, C, h, w], `scales` (1 to 4 ints in 1 .. 8; the decoders use
+    (1, 2, 3, 6)) and `branch_channels` (K_k >= 1 per scale).  cat [B, C + sum K_k, h, w] holds conv5 in its first C channels,
+    bit for bit; its other channels are UNWRITTEN until segm_ppm_fill.  p_k equals F.adaptive_avg_pool2d(conv5, s_k).
+    Differentiable in conv5 through both cat and every p_k.  A wrong type or dtype raises TypeError, a wrong shape or size
+    ValueError, a CPU tensor NotImplementedError; the library is not touched before."""
+    try:
+        scales, branch_channels = [int(s) for s in scales], [int(k) for k in branch_channels]
+    except TypeError:
+        raise TypeError('scales and branch_channels must be sequences of ints')
+    if not 1 <= len(scales) <= SEGM_PPM_MAX_SCALES or len(branch_channels) != len(scales):
+        raise ValueError('1 to %d scales with as many branch_channels, got %r and %r' % (SEGM_PPM_MAX_SCALES, scales, branch_channels))
+    if any(s < 1 or s > SEGM_PPM_MAX_SIDE for s in scales) or any(k < 1 for k in branch_channels):
+        raise ValueError('scales must lie in 1 .. %d and branch_channels be >= 1, got %r and %r' % (SEGM_PPM_MAX_SIDE, scales, branch_channels))
+    if isinstance(conv5, torch.Tensor) and conv5.dtype == torch.float32 and conv5.dim() != 4:
+        raise ValueError('conv5 must be fp32 [B, C, h, w], got %s' % (tuple(conv5.shape),))
+    _ppm_tensor(conv5, 'conv5')
+    B, C, h, w = conv5.shape
+    if B * (C + sum(branch_channels)) * h * w >= 2 ** 31:
+        raise ValueError('B * (C + sum K) * h * w = %d must stay below 2^31' % (B * (C + sum(branch_channels)) * h * w))
+    if not conv5.is_cuda:
+        raise NotImplementedError('conv5 is on %s; the pyramid pooling kernels only run on the GPU' % (conv5.device,))
+    return SegmPpmPoolFn.apply(conv5, tuple(scales), tuple(branch_channels))
+
+
+def segm_ppm_fill(cat, C, *ys):
+    """Writes the bilinear upsampling (align_corners=False) of the branch outputs y_1 .. y_S (as arguments, or one list of
+    them), y_k CUDA fp32 [B, K_k, s_k, s_k], into cat[:, C:] IN PLACE and returns cat: branch k takes the K_k channels after
+    C + sum_{k' < k} K_k'.  cat must be the contiguous [B, C + sum K_k, h, w] tensor of segm_ppm_pool.  Differentiable in cat
+    and every y_k.  A wrong type or dtype raises TypeError, a wrong shape ValueError, a CPU tensor NotImplementedError; the
+    library is not touched before."""
+    ys = list(ys[0]) if len(ys) == 1 and isinstance(ys[0], (list, tuple)) else list(ys)
+    if not 1 <= len(ys) <= SEGM_PPM_MAX_SCALES:
+        raise ValueError('1 to %d branch outputs, got %d' % (SEGM_PPM_MAX_SCALES, len(ys)))
+    for t, name in [(cat, 'cat')] + [(y, 'y[%d]' % k) for k, y in enumerate(ys)]:
+        if isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() != 4:
+            raise ValueError('%s must be fp32 with four axes, got %s' % (name, tuple(t.shape)))
+    C = int(C)
+    devs = [t.device for t in [cat] + ys if isinstance(t, torch.Tensor)]
+    for t, name in [(cat, 'cat')] + [(y, 'y[%d]' % k) for k, y in enumerate(ys)]:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+        if t.dtype != torch.float32:
+            raise TypeError('%s must be torch.float32, got %s' % (name, t.dtype))
+    B, Ctot, h, w = cat.shape
+    for k, y in enumerate(ys):
+        if y.shape[0] != B or y.shape[1] < 1 or y.shape[2] != y.shape[3] or not 1 <= y.shape[2] <= SEGM_PPM_MAX_SIDE:
+            raise ValueError('y[%d] must be [%d, K, s, s] with K >= 1 and s in 1 .. %d, got %s' % (k, B, SEGM_PPM_MAX_SIDE, tuple(y.shape)))
+    if C < 1 or C + sum(int(y.shape[1]) for y in ys) != Ctot or min(cat.shape) < 1:
+        raise ValueError('cat has %d channels; C = %d and the branches hold %r' % (Ctot, C, [int(y.shape[1]) for y in ys]))
+    if B * Ctot * h * w >= 2 ** 31:
+        raise ValueError('B * Ctot * h * w = %d must stay below 2^31' % (B * Ctot * h * w))
+    if any(d != devs[0] for d in devs):
+        raise ValueError('cat and the branch outputs are on different devices: %r' % (devs,))
+    if not cat.is_cuda:
+        raise NotImplementedError('cat is on %s; the pyramid pooling kernels only run on the GPU' % (cat.device,))
+    if not cat.is_contiguous():
+        raise ValueError('cat must be contiguous: it is written in place')
+    return SegmPpmFillFn.apply(cat, C, *ys)

@@ -74,7 +74,8 @@ const char* sdn_last_error(void);
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
  * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
  * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added; 20: sdn_segm_loss_fwd,
- * sdn_segm_loss_bwd added).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
+ * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added -- new entry
+ * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
 #define SDN_ABI_VERSION 20
@@ -853,6 +854,39 @@ int sdn_segm_loss_fwd(const float* scores, const float* scores_deepsup, const in
 int sdn_segm_loss_bwd(const float* scores, const float* scores_deepsup, const int64_t* seg_label, int B, int C, int h, int w,
                       float deep_sup_scale, const float* lse, const int64_t* counts, const float* grad_out, float* grad_scores,
                       float* grad_scores_deepsup, sdnStream stream);
+
+/* ---- the pyramid pooling module of the semantic decoders: semantic/models.py:336-346, 387-397 (csrc/segm_ppm.hip) -----------------
+ * PPMBilinear / PPMBilinearDeepsup.forward: for every pool scale AdaptiveAvgPool2d(s) of conv5, the branch's 1 x 1 conv / BN / ReLU,
+ * a bilinear upsample back to conv5's size, then torch.cat([conv5, branch outputs], 1): nine full-tensor launches forward, about
+ * twice that backward.  The four calls below go around the caller's branch modules, two launches forward and two backward.
+ * Everything is fp32, contiguous NCHW, DEVICE; scales, branch_channels, y, grad_y, grad_p are HOST arrays of S entries
+ * (1 <= S <= 4, 1 <= scales[k] <= 8, branch_channels[k] = K_k >= 1; Ctot = C + sum K_k; B * Ctot * h * w < 2^31).
+ *
+ * sdn_segm_ppm_pool, one launch: conv5 [B, C, h, w] is read once; cat [B, Ctot, h, w] gets conv5 in its first C channels, bit for
+ *   bit, its other channels are left alone; pooled holds p_0 .. p_{S-1}, p_k [B, C, s_k, s_k] contiguous, one after the other
+ *   (p_k begins at float B * C * sum_{k' < k} s_k'^2).  Bins are torch's: rows floor(i h / s) up to ceil((i + 1) h / s), columns
+ *   likewise, value = sum / area; the sum is taken in fp64, columns then rows in ascending order, and rounded once.
+ * sdn_segm_ppm_fill, one launch for all branches: y[k] [B, K_k, s_k, s_k], the branch outputs; channel C + sum_{k' < k} K_k' + j
+ *   of cat becomes the bilinear upsampling of y[k][:, j] to h x w, align_corners=False, torch's fp32 rule: scale = (float)s / n,
+ *   src = max(scale * (o + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = min(i0 + 1, s - 1), lambda = src - i0.  Every element of those
+ *   channels is written, nothing else.
+ * sdn_segm_ppm_fill_bwd, one launch: grad_cat [B, Ctot, h, w]; grad_y[k] [B, K_k, s_k, s_k] = the transposed interpolation of
+ *   the planes grad_cat[:, C + ...], summed in fp64 in a fixed order.  A NULL grad_y[k] is skipped and its planes are not read
+ *   (not all may be NULL); the first C channels are not read.
+ * sdn_segm_ppm_pool_bwd, one launch: grad_conv5 [B, C, h, w] = grad_cat[:, :C] + for every scale the sum of grad_p[k][bin] /
+ *   area(bin) over the bins that cover the pixel (one or two per axis when h >= s, more when h < s).  grad_cat may be NULL,
+ *   grad_p may be NULL and so may any grad_p[k], but not all of them.  branch_channels is needed for grad_cat's stride.
+ * SDN_EINVAL with a message before any launch for a NULL or misaligned pointer and for sizes outside the above.  16-byte loads and
+ * stores when w % 4 == 0 and the bases are 16-byte aligned, scalar ones otherwise.  No atomics, nothing to zero; identical from
+ * run to run; nothing crosses to the host. */
+int sdn_segm_ppm_pool(const float* conv5, int B, int C, int h, int w, const int* scales, const int* branch_channels, int S, float* cat,
+                      float* pooled, sdnStream stream);
+int sdn_segm_ppm_fill(const float* const* y, int B, int C, int h, int w, const int* scales, const int* branch_channels, int S, float* cat,
+                      sdnStream stream);
+int sdn_segm_ppm_fill_bwd(const float* grad_cat, int B, int C, int h, int w, const int* scales, const int* branch_channels, int S,
+                          float* const* grad_y, sdnStream stream);
+int sdn_segm_ppm_pool_bwd(const float* grad_cat, const float* const* grad_p, int B, int C, int h, int w, const int* scales,
+                          const int* branch_channels, int S, float* grad_conv5, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
