@@ -106,18 +106,23 @@ __global__ void k_bn_finalize(const double* __restrict__ sums, double count, int
     ss[c] = make_float2(sc, b - m * sc);
 }
 
-// out = f(x * scale + shift + res), f = ReLU when relu
-__global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ x, const float2* __restrict__ ss,
+// out = f((x - mean) * scale + beta + res), f = ReLU when relu.  Centred, as torch evaluates it: x * scale + shift rounds at
+// the size of mean * scale and loses |mean| * rstd * 2^-24 of the output.  That shows where the batch variance is next to 0 and
+// rstd is large: 1e-5 of the output with 2 rows (two values of a channel 0.007 apart around 3: rstd 270) and with 1 row in
+// training (rstd 316), tests/test_gpu_conv_companions.py c4_rows_2_c4n_1 and c8_rows_1_train_formula_only.  (scale, shift)
+// is still written to ss for the caller; the shift is not read here.
+__global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ x, const float2* __restrict__ mr,
+                                                  const float2* __restrict__ ss, const float* __restrict__ beta,
                                                   const float* __restrict__ res, float* __restrict__ out, long rows,
                                                   int C, long rows_per_block, int relu)
 {
     const BnLay L(C);
-    float sc[4], sh[4];
+    float mean[4], sc[4], bt[4];
 #pragma unroll
     for (int j = 0; j < 4; j++) {
-        const float2 v = ss[L.c0 + j];
-        sc[j] = v.x;
-        sh[j] = v.y;
+        mean[j] = mr[L.c0 + j].x;
+        sc[j] = ss[L.c0 + j].x;
+        bt[j] = beta ? beta[L.c0 + j] : 0.f;
     }
     const long lo = (long)blockIdx.x * rows_per_block, hi = min(lo + rows_per_block, rows);
     for (long p = lo + L.prow; p < hi; p += L.pstep) {
@@ -127,7 +132,7 @@ __global__ __launch_bounds__(256) void k_bn_apply(const float* __restrict__ x, c
         if (res) r = *reinterpret_cast<const f32x4*>(res + off);
 #pragma unroll
         for (int j = 0; j < 4; j++) {
-            float y = v[j] * sc[j] + sh[j] + r[j];
+            float y = (v[j] - mean[j]) * sc[j] + bt[j] + r[j];
             v[j] = relu ? fmaxf(y, 0.f) : y;
         }
         *reinterpret_cast<f32x4*>(out + off) = v;
@@ -350,7 +355,7 @@ SDN_API int sdn_bn_forward(const float* x, long rows, int C, const float* gamma,
     }
     k_bn_finalize<<<cdiv(C, 256), 256, 0, st>>>(sums, (double)rows, C, gamma, beta, running_mean, running_var, momentum, eps,
                                                training, (float2*)mr, (float2*)ss);
-    k_bn_apply<<<grid, 256, 0, st>>>(x, (const float2*)ss, res, out, rows, C, rpb, relu);
+    k_bn_apply<<<grid, 256, 0, st>>>(x, (const float2*)mr, (const float2*)ss, beta, res, out, rows, C, rpb, relu);
     return check_launch("sdn_bn_forward");
 }
 

@@ -370,8 +370,9 @@ int sdn_conv_unpack_grad(const float* dw, int R, int C, long sr, long sc, const 
  * Its convolutions are sdn_conv_gemm / sdn_conv_wgrad launches (bias-free 7x7 s2, 3x3 s1/s2, 1x1 s2); the entries below are
  * the rest of the network on channels-last fp32 tensors [rows = N*H*W, C] (C % 4 == 0; C <= 64 a power of two, else C % 64 == 0).
  *
- * nn.BatchNorm2d (+ the BasicBlock tail `relu(bn(x) + identity)`):  out = f(x * scale + shift + res), f = ReLU when relu,
- * scale = gamma * rstd, shift = beta - mean * scale.  training: batch mean / biased variance over the rows (sums: [C,2] fp64
+ * nn.BatchNorm2d (+ the BasicBlock tail `relu(bn(x) + identity)`):  out = f((x - mean) * scale + beta + res), f = ReLU when
+ * relu, scale = gamma * rstd (evaluated centred, as torch does; shift = beta - mean * scale is only reported in ss).
+ * training: batch mean / biased variance over the rows (sums: [C,2] fp64
  * scratch), running_mean / running_var (may be NULL) updated with momentum and the unbiased variance; eval: the running
  * statistics.  mr [C,2] = (mean, rstd) and ss [C,2] = (scale, shift) are written for the backward pass.  res may be NULL. */
 int sdn_bn_forward(const float* x, long rows, int C, const float* gamma, const float* beta, float* running_mean,
