@@ -122,6 +122,10 @@ def _declare(L):
     sig['sdn_segm_ppm_fill'] = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]
     sig['sdn_segm_ppm_fill_bwd'] = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]
     sig['sdn_segm_ppm_pool_bwd'] = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp, _ci, _vp, _vp]
+    sig['sdn_encode_maps'] = [_vp, _ci, _vp, _ci, _vp, _ci, _ci, _ci, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
+    sig['sdn_inst_index_workspace_bytes'] = [ctypes.POINTER(_sz)]
+    sig['sdn_inst_index_build'] = [_vp, _ci, _ci, _ci, _ci, _vp, _sz, _vp, _vp, _cl, _vp]
+    sig['sdn_inst_index_rank'] = [_vp, _ci, _ci, _ci, _ci, _vp, _sz, _vp, _vp, _vp]
     sig['sdn_train_losses_scratch'] = [_ci, _ci, _cl, ctypes.POINTER(_sz)]
     sig['sdn_train_losses_fwd'] = [_vp] * 7 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp]
     sig['sdn_train_losses_bwd'] = [_vp] * 6 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd] + [_vp] * 9 + [_vp]
@@ -160,7 +164,7 @@ def _declare(L):
         try:
             fn = getattr(L, name)
         except AttributeError:
-            # entry points added without a revision bump (the sdn_segm_ppm_* family): a library built before them is stale
+            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*): a library built before them is stale
             raise SdnHipError('%s does not export %s -- rebuild it (`python __graft_entry__.py build`)' % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = _ci
@@ -205,6 +209,7 @@ def exported_symbols():
             'sdn_train_losses_scratch', 'sdn_train_losses_fwd', 'sdn_train_losses_bwd',
             'sdn_segm_fuse', 'sdn_segm_labels_from_colors', 'sdn_segm_confusion', 'sdn_segm_train_batch', 'sdn_segm_loss_fwd', 'sdn_segm_loss_bwd',
             'sdn_segm_ppm_pool', 'sdn_segm_ppm_fill', 'sdn_segm_ppm_fill_bwd', 'sdn_segm_ppm_pool_bwd',
+            'sdn_encode_maps', 'sdn_inst_index_workspace_bytes', 'sdn_inst_index_build', 'sdn_inst_index_rank',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',

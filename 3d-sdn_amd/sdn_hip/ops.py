@@ -1760,3 +1760,115 @@ def segm_ppm_fill(cat, C, *ys):
     if not cat.is_contiguous():
         raise ValueError('cat must be contiguous: it is written in place')
     return SegmPpmFillFn.apply(cat, C, *ys)
+
+
+# ---- the input side of the textural networks (csrc/encode_input.hip) ---------------------------------------------------------------
+MAP_U8, MAP_I16, MAP_I32, MAP_F32 = 0, 1, 2, 3                 # include/sdn_hip.h: SDN_MAP_*
+ENCODE_MAX_CHANNELS = 256                                       # csrc/encode_input_check.h: ENC_MAX_CHANNELS
+INST_KEY_MIN, INST_KEY_BITS = -32768, 1 << 21                   # the key window [INST_KEY_MIN, INST_KEY_MIN + INST_KEY_BITS)
+INST_HEAD_AT = (INST_KEY_BITS // 32) * 4                        # byte of (K, overflow) in the workspace, behind the bitmap
+_MAP_DTYPES = {torch.uint8: MAP_U8, torch.int16: MAP_I16, torch.int32: MAP_I32, torch.float32: MAP_F32}
+ENCODE_LABEL_DTYPES = (torch.uint8, torch.int32, torch.float32)
+ENCODE_INST_DTYPES = (torch.int16, torch.int32, torch.float32)
+ENCODE_POSE_DTYPES = (torch.int32, torch.float32)
+
+
+def _index_map(t, name, dtypes, like=None):
+    """a contiguous [N, 1, H, W] map of one of `dtypes`, of `like`'s shape and device when given"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if t.dtype not in dtypes:
+        raise TypeError('%s must be one of %s, got %s' % (name, ', '.join(str(d) for d in dtypes), t.dtype))
+    if t.dim() != 4 or t.shape[1] != 1 or min(t.shape) < 1:
+        raise ValueError('%s must be [N, 1, H, W] without an empty axis, got %s' % (name, tuple(t.shape)))
+    if like is not None and (t.shape != like.shape or t.device != like.device):
+        raise ValueError('%s is %s on %s, label %s on %s' % (name, tuple(t.shape), t.device, tuple(like.shape), like.device))
+    if t.numel() >= 2 ** 31:
+        raise ValueError('%s holds %d elements; the sizes must stay below 2^31' % (name, t.numel()))
+
+
+def encode_maps(label, inst, pose, label_nc, pose_ch):
+    """The label planes, edge plane and pose planes of Pix2PixHDModel.encode_input in one launch (sdn_encode_maps;
+    textural/models/pix2pixHD_model.py:124-166, 343-349).  label CUDA [N, 1, H, W] uint8 / int32 / float32; inst likewise int16 /
+    int32 / float32, or None for no edge plane; pose int32 / float32, or None with pose_ch 0.  1 <= label_nc <= 256,
+    pose_ch = feat_pose_num_bins + 1 <= 256.  Returns (input_label fp32 [N, label_nc (+ 1 with inst), H, W],
+    pose_onehot fp32 [N, pose_ch, H, W] or None, bad int32 [2] on the device): the planes of `scatter_(1, map.long(), 1.0)` and
+    get_edges; an index outside [0, channels) or a NaN sets no plane and is counted in bad[0] (label) / bad[1] (pose), where the
+    reference's scatter_ trips a device-side assert.  A map that is not contiguous is copied.  A wrong type or dtype raises
+    TypeError, a wrong shape or size ValueError, a CPU tensor NotImplementedError; the library is not touched before."""
+    label_nc, pose_ch = int(label_nc), int(pose_ch)
+    _index_map(label, 'label', ENCODE_LABEL_DTYPES)
+    if inst is not None:
+        _index_map(inst, 'inst', ENCODE_INST_DTYPES, label)
+    if not 1 <= label_nc <= ENCODE_MAX_CHANNELS or not 0 <= pose_ch <= ENCODE_MAX_CHANNELS:
+        raise ValueError('label_nc must lie in 1 .. %d and pose_ch in 0 .. %d, got %d and %d'
+                         % (ENCODE_MAX_CHANNELS, ENCODE_MAX_CHANNELS, label_nc, pose_ch))
+    if (pose is None) != (pose_ch == 0):
+        raise ValueError('pose and pose_ch go together: pose is %s with pose_ch %d' % ('None' if pose is None else 'given', pose_ch))
+    if pose is not None:
+        _index_map(pose, 'pose', ENCODE_POSE_DTYPES, label)
+    N, _, H, W = label.shape
+    planes = label_nc + (0 if inst is None else 1)
+    if N * max(planes, pose_ch) * H * W >= 2 ** 31:
+        raise ValueError('N * channels * H * W = %d must stay below 2^31' % (N * max(planes, pose_ch) * H * W))
+    if label.device.type != 'cuda':
+        raise NotImplementedError('label is on %s; the input encoding kernels only run on the GPU' % (label.device,))
+    label = label.contiguous()
+    inst = None if inst is None else inst.contiguous()
+    pose = None if pose is None else pose.contiguous()
+    dev = label.device
+    with torch.cuda.device(dev):
+        input_label = torch.empty(N, planes, H, W, dtype=torch.float32, device=dev)
+        pose_onehot = torch.empty(N, pose_ch, H, W, dtype=torch.float32, device=dev) if pose_ch else None
+        bad = torch.empty(2, dtype=torch.int32, device=dev)
+        check(lib().sdn_encode_maps(ptr(label), _MAP_DTYPES[label.dtype], ptr(inst), _MAP_DTYPES[inst.dtype] if inst is not None else 0,
+                                    ptr(pose), _MAP_DTYPES[pose.dtype] if pose is not None else 0, N, H, W, label_nc, pose_ch,
+                                    ptr(input_label), ptr(pose_onehot), ptr(bad), stream()))
+    return input_label, pose_onehot, bad
+
+
+_inst_workspaces = {}
+
+
+def inst_index_workspace(device):
+    """The workspace of sdn_inst_index_* on `device` (a presence bitmap of the key window, its prefix counts, K and overflow: 512
+    KiB + 16 bytes), one per device and calling stream; sdn_inst_index_build clears what it needs."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    ws = _inst_workspaces.get(key)
+    if ws is None:
+        n = ctypes.c_size_t()
+        check(lib().sdn_inst_index_workspace_bytes(ctypes.byref(n)))
+        ws = _inst_workspaces[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
+    return ws
+
+
+def inst_index(inst, with_counts=False):
+    """The instance numbering of Encoder.forward without a sort (sdn_inst_index_build / _rank; textural/models/networks.py:310-325:
+    inst[i] = inst[i] * bs + i, then the unique values of every pixel).  inst CUDA contiguous [N, 1, H, W] int16 / int32 /
+    float32; it is DISAMBIGUATED IN PLACE, as the reference does.  Returns (ids int64 [K] ascending, seg int32 [N, H, W] with
+    ids[seg] == inst.long(), counts int64 [K] pixels per id or None, info): what torch.unique(inst.reshape(-1).long(),
+    return_inverse=True, return_counts=with_counts) gives.  One 8-byte copy to the host (K and overflow).  info['path'] is
+    'device', or 'torch' when info['overflow'] pixels had a key outside [-32768, 2^21 - 32768) or NaN / Inf: torch.unique then
+    runs on the already disambiguated map.  A wrong type or dtype raises TypeError, a wrong shape or a map that is not contiguous
+    ValueError, a CPU tensor NotImplementedError; the library is not touched before."""
+    _index_map(inst, 'inst', ENCODE_INST_DTYPES)
+    if inst.device.type != 'cuda':
+        raise NotImplementedError('inst is on %s; the instance numbering kernels only run on the GPU' % (inst.device,))
+    if not inst.is_contiguous():
+        raise ValueError('inst must be contiguous: it is disambiguated in place')
+    N, _, H, W = inst.shape
+    dev = inst.device
+    dt = _MAP_DTYPES[inst.dtype]
+    with torch.cuda.device(dev):
+        ws = inst_index_workspace(dev)
+        cap = min(N * H * W, INST_KEY_BITS)
+        ids = torch.empty(cap, dtype=torch.int64, device=dev)
+        counts = torch.empty(cap, dtype=torch.int64, device=dev) if with_counts else None
+        seg = torch.empty(N, H, W, dtype=torch.int32, device=dev)
+        check(lib().sdn_inst_index_build(ptr(inst), dt, N, H, W, ptr(ws), ws.numel(), ptr(ids), ptr(counts), cap, stream()))
+        check(lib().sdn_inst_index_rank(ptr(inst), dt, N, H, W, ptr(ws), ws.numel(), ptr(seg), ptr(counts), stream()))
+        K, overflow = ws[INST_HEAD_AT:INST_HEAD_AT + 8].view(torch.int32).tolist()   # the one copy to the host
+    if overflow:
+        got = torch.unique(inst.reshape(-1).long(), return_inverse=True, return_counts=with_counts)
+        return got[0], got[1].to(torch.int32).reshape(N, H, W), (got[2] if with_counts else None), {'path': 'torch', 'overflow': overflow}
+    return ids[:K], seg, (counts[:K] if with_counts else None), {'path': 'device', 'overflow': 0}

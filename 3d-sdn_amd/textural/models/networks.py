@@ -334,6 +334,8 @@ class Encoder(nn.Module, _Fused):
         layers += _c7s1(ngf, output_nc, None, nn.Tanh())
         self.model = nn.Sequential(*layers)
 
+    last_index_info = None   # info of the last instance numbering on the device path ({'path': 'device' | 'torch', 'overflow': n})
+
     @staticmethod
     def _disambiguate(inst):
         """`inst[i] = inst[i] * batch + i` in place, as the reference does (networks.py:313-316): the same id in two
@@ -345,11 +347,17 @@ class Encoder(nn.Module, _Fused):
 
     def _pooled(self, input, inst, with_counts=False):
         feats = self._chain('model', self.model, self.input_nc)(input)[0]          # [N, C, H, W]
-        inst = self._disambiguate(inst)
-        ids, inverse, *counts = torch.unique(inst.reshape(-1).long(), return_inverse=True,
-                                             return_counts=with_counts)            # one sync for the id count
         N, C, H, W = feats.shape
-        seg = inverse.to(torch.int32).reshape(N, H, W)
+        from . import input_maps
+        if input_maps.device_path_enabled() and input_maps.instance_index_supported(inst) and tuple(inst.shape) == (N, 1, H, W):
+            # the numbering without a sort (csrc/encode_input.hip); inst is disambiguated in place there; one 8-byte copy for K
+            ids, seg, cnt, self.last_index_info = input_maps.instance_index(inst, with_counts)
+            counts = [cnt] if with_counts else []
+        else:
+            inst = self._disambiguate(inst)
+            ids, inverse, *counts = torch.unique(inst.reshape(-1).long(), return_inverse=True,
+                                                 return_counts=with_counts)        # one sync for the id count
+            seg = inverse.to(torch.int32).reshape(N, H, W)
         out, means = _ops.SegmentMeanFn.apply(feats.contiguous(), seg, int(ids.numel()))
         return (out, ids, means, counts[0]) if with_counts else (out, ids, means)
 

@@ -172,16 +172,56 @@ class Pix2PixHDModel(BaseModel):
         edge[:, :, :-1, :] |= dy
         return edge.float()
 
+    last_encode_bad = None   # int32 [2] on the device after a fused encode_input: label / pose pixels with an index out of range
+
+    def _encode_maps_fused(self, label_map, inst_map, pose_map, dev):
+        """(input_label, inst_map, pose_map) through input_maps.encode_maps -- the label planes, the edge plane and the one-hot pose
+        planes in one launch -- or None where the torch expressions of encode_input run: a map that is not a CUDA tensor on the
+        model's device, a dtype or layout the kernel does not take, label_nc 0, or SDN_ENCODE_DEVICE=0.  Same values, dtypes and
+        shapes either way; the count of out-of-range indices (which the torch expressions answer with a device-side assert)
+        stays on the device in self.last_encode_bad."""
+        from . import input_maps
+        opt = self.opt
+        if opt.label_nc == 0 or not input_maps.device_path_enabled():
+            return None
+        inst = None if opt.no_instance else inst_map
+        onehot_pose = bool(self.use_features and opt.feat_pose and opt.feat_pose_num_bins)
+        pose = pose_map if onehot_pose else None
+        pose_ch = opt.feat_pose_num_bins + 1 if onehot_pose else 0
+        if (inst is None and not opt.no_instance) or (pose is None and onehot_pose):
+            return None
+        maps = [m for m in (label_map, inst, pose) if m is not None]
+        if any(not isinstance(m, torch.Tensor) or m.device != dev for m in maps):
+            return None
+        if not input_maps.encode_maps_supported(label_map, inst, pose, opt.label_nc, pose_ch):
+            return None
+        with torch.no_grad():
+            input_label, pose_onehot, self.last_encode_bad = input_maps.encode_maps(
+                label_map.detach(), None if inst is None else inst.detach(), None if pose is None else pose.detach(), opt.label_nc, pose_ch)
+            if inst is not None:
+                inst_map = inst.detach()
+            if onehot_pose:
+                pose_map = pose_onehot
+            elif self.use_features and opt.feat_pose:
+                pose_map = pose_map.detach().to(dev)
+        return input_label, inst_map, pose_map
+
     def encode_input(self, label_map, inst_map=None, real_image=None, feat_map=None, pose_map=None, normal_map=None,
                      depth_map=None, infer=False):
         dev = self._device()
         opt = self.opt
+        fused = self._encode_maps_fused(label_map, inst_map, pose_map, dev)
+        if fused is not None:
+            input_label, inst_map, pose_map = fused
+            label_map = None
         with torch.no_grad():
-            if opt.label_nc == 0:
+            if fused is not None:
+                pass
+            elif opt.label_nc == 0:
                 input_label = label_map.detach().to(dev)
             else:
                 input_label = self._one_hot(label_map.detach().to(dev), opt.label_nc)
-            if not opt.no_instance:
+            if fused is None and not opt.no_instance:
                 inst_map = inst_map.detach().to(dev)
                 input_label = torch.cat((input_label, self.get_edges(inst_map)), dim=1)
             if real_image is not None:
@@ -189,7 +229,7 @@ class Pix2PixHDModel(BaseModel):
             if self.use_features:
                 if opt.load_features:
                     feat_map = feat_map.detach().to(dev)
-                if opt.feat_pose:
+                if opt.feat_pose and fused is None:
                     pose_map = pose_map.detach().to(dev)
                     if opt.feat_pose_num_bins:
                         pose_map = self._one_hot(pose_map, opt.feat_pose_num_bins + 1)

@@ -74,7 +74,8 @@ const char* sdn_last_error(void);
  * added; 15: sdn_train_rois, sdn_train_crops added; 16: sdn_train_losses_scratch, sdn_train_losses_fwd, sdn_train_losses_bwd
  * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
  * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added; 20: sdn_segm_loss_fwd,
- * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added -- new entry
+ * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added; still 20: sdn_encode_maps,
+ * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -888,6 +889,49 @@ int sdn_segm_ppm_fill_bwd(const float* grad_cat, int B, int C, int h, int w, con
                           float* const* grad_y, sdnStream stream);
 int sdn_segm_ppm_pool_bwd(const float* grad_cat, const float* const* grad_p, int B, int C, int h, int w, const int* scales,
                           const int* branch_channels, int S, float* grad_conv5, sdnStream stream);
+
+/* ---- the input side of the textural networks (csrc/encode_input.hip) ------------------------------------------------------------------
+ * Element types of the index and instance maps below: */
+#define SDN_MAP_U8 0
+#define SDN_MAP_I16 1
+#define SDN_MAP_I32 2
+#define SDN_MAP_F32 3
+/* sdn_encode_maps, one kernel launch: the label planes, the edge plane and the pose planes of Pix2PixHDModel.encode_input
+ * (textural/models/pix2pixHD_model.py:124-166 with get_edges :343-349: zeros + long + scatter_ twice, about ten slice / compare / or
+ * launches and a cat).  All maps are contiguous [N, 1, H, W], DEVICE: label uint8 / int32 / float32; inst int16 / int32 / float32 or
+ * NULL (no edge plane); pose int32 / float32, read when pose_ch > 0.  1 <= label_nc <= 256, 0 <= pose_ch <= 256
+ * (feat_pose_num_bins + 1, or 0 for none).
+ *   input_label fp32 [N, label_nc (+ 1 with inst), H, W]: plane trunc(label) holds 1.0f (the value truncated toward zero, as
+ *     .long() does: -0.5 selects plane 0), every other label plane 0.0f; the last plane is 1.0f where the instance value differs
+ *     (!= in the map's own dtype: NaN differs from NaN) from its left, right, upper or lower neighbour inside the map.
+ *   pose_onehot fp32 [N, pose_ch, H, W] likewise from pose; not touched (may be NULL) when pose_ch == 0.
+ *   bad int32 [2]: where the reference's scatter_ trips a device-side assert -- an index outside [0, channels) or a NaN -- no plane
+ *     is set and the pixel is counted, bad[0] for label, bad[1] for pose (the convention of sdn_segm_loss_fwd's counts[2]).
+ * Every element of both outputs is written; the caller zeroes nothing (the entry point clears the 8 bytes of bad on the stream).
+ * 16-byte plane stores when W % 4 == 0 and all bases are 16-byte aligned, scalar ones otherwise.  Nothing crosses to the host.
+ *
+ * sdn_inst_index_*: the instance numbering of Encoder.forward (textural/models/networks.py:310-325: inst[i] = inst[i] * bs + i,
+ * then np.unique over every pixel) without a sort.  The key of a pixel is the disambiguated value truncated toward zero; the
+ * product and sum are taken in the map's own dtype (fp32: two roundings; int32, int16: wraparound).  Keys live in the window
+ * [-32768, 2^21 - 32768); workspace: sdn_inst_index_workspace_bytes (a presence bitmap, the words' prefix counts, K, overflow),
+ * aligned to 16 bytes, caller-owned, cleared by sdn_inst_index_build itself.
+ * sdn_inst_index_build, two launches: writes the disambiguated values back into inst [N, 1, H, W] in place (as the reference does)
+ *   and sets every key's bit; then one workgroup forms the prefix counts, K and ids int64 [id_capacity >= min(N H W, 2^21)], the
+ *   first K entries ascending, and clears counts int64 [id_capacity] (may be NULL) in its first K entries.  int32 [2] at byte
+ *   65536 * 4 of the workspace: K and overflow, the number of pixels whose key lies outside the window or is NaN / Inf -- the
+ *   one 8-byte copy a caller needs before it can size its results.  With overflow != 0 the numbering is incomplete.
+ * sdn_inst_index_rank, one launch, after build on the same stream, inst as build left it: seg int32 [N, H, W] = the position of
+ *   the pixel's key in ids (-1 outside the window); counts [k] += the pixels of id k when not NULL (integer atomics, summed per
+ *   lane and per workgroup first).  Identical from run to run.
+ * SDN_EINVAL with a message before any launch for a NULL or misaligned pointer, an unsupported dtype, sizes of 2^31 or more, channel
+ * counts outside the above, or a workspace / ids buffer that is too small. */
+int sdn_encode_maps(const void* label, int label_dtype, const void* inst, int inst_dtype, const void* pose, int pose_dtype, int N, int H,
+                    int W, int label_nc, int pose_ch, float* input_label, float* pose_onehot, int32_t* bad, sdnStream stream);
+int sdn_inst_index_workspace_bytes(size_t* bytes);
+int sdn_inst_index_build(void* inst, int inst_dtype, int N, int H, int W, void* workspace, size_t workspace_bytes, int64_t* ids,
+                         int64_t* counts, long id_capacity, sdnStream stream);
+int sdn_inst_index_rank(const void* inst, int inst_dtype, int N, int H, int W, const void* workspace, size_t workspace_bytes,
+                        int32_t* seg, int64_t* counts, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
