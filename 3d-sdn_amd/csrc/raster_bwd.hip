@@ -17,6 +17,15 @@
 //   Every partial sum has a fixed order, so the result is deterministic run to run (the reference's is too);
 //   it differs from the reference's strictly serial sum by float re-association only (~1e-7 relative).
 //   Faces whose chunks do not fit the workspace fall back to the literal serial walk inside k_edge_reduce.
+//   Silhouette fast path (only alpha is differentiated): k_hmap + k_compact_rows build the rows' non-zero lists,
+//     k_edge_scan_sil (64 edge pixels per wave) files every "out" scan under its row, k_edge_rows evaluates a row's
+//     scans from LDS, k_chunk_sum adds them to their chunks and k_edge_reduce runs as above.
+//   Frame step (that path with a vertex sink: sdn_render_maps_bwd differentiating the silhouette alone):
+//     k_edge_segments (1 thread / chunk slot) replaces k_chunk_sum + k_edge_reduce: a face's chunks lie side by side
+//     in (edge, axis) order, so the first chunk of every (face, edge, axis) run sums the run in chunk order and adds
+//     the two sums to the edge's end points -- no pass over the faces (nine in ten are hidden), no face coordinates,
+//     no second edge_walk.  The faces of the serial fallback are listed by k_edge_plan and walked by the kernel's
+//     first few workgroups.
 //
 //   K6 + K7 (rasterize.py:756-789, 800-844) in k_bwd_pixels: per covered pixel, scatter the colour gradient into
 //   the face's texture (or per-face colour) and the depth gradient into the winning face's 9 coordinates with
@@ -52,7 +61,8 @@ struct BwdParams {
     // K5 plan
     uint32_t* visible;      // [bs*nf]
     int32_t* chunk_base;    // [bs*nf]  >= 0 first chunk, -1 serial fallback, -2 contributes nothing
-    uint32_t* counter;      // [1] chunks allocated so far
+                            //          (k_edge_segments' path: the list of the serial-fallback faces instead, counter[1] of them)
+    uint32_t* counter;      // [2] chunks allocated so far; faces on the serial-fallback list
     uint4* chunk_desc;      // [cap] {global face, edge*2+axis, d0_start, count}
     float2* chunk_out;      // [cap]
     const float* hmap;      // [bs,S,S]  silhouette-only fast path: max(-g_alpha, 0) on background pixels, else 0
@@ -73,6 +83,16 @@ struct BwdParams {
     int ts, bs, nf, S, flags;
     VertexSink sink;         // sink.grad_verts != null: k_edge_reduce adds to the vertices instead of writing grad_faces rows
 };
+
+// The frame step's path (vertex sink + silhouette fast path): k_edge_segments instead of k_chunk_sum + k_edge_reduce.
+__host__ __device__ __forceinline__ bool segment_path(const BwdParams& P)
+{
+#ifdef SDN_LAB_EDGE_PER_FACE   // (lab: k_chunk_sum + k_edge_reduce on every path, for A/B builds)
+    return false;
+#else
+    return P.sink.grad_verts != nullptr && P.nz_cnt != nullptr;
+#endif
+}
 
 // One "out" scan of K5 (rasterize.py:600-656) reduced to what its terms need: sum over the row's non-zero list [k0, k1) of
 // val / (t * (pos - cross) +- eps) for the edge's two end points.
@@ -391,7 +411,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_edge_plan(const BwdParams P)
 {
     const long i = (long)blockIdx.x * PLAN_THREADS + threadIdx.x;
     const long total = (long)P.bs * P.nf;
-    if (P.sink.grad_verts) {   // what k_edge_reduce's atomics add onto (one launch ahead of them on the stream)
+    if (P.sink.grad_verts) {   // what k_edge_reduce's / k_edge_segments' atomics add onto (one launch ahead of them on the stream)
         const long n = (long)P.bs * P.sink.nv * 3;
         for (long k = i; k < n; k += (long)gridDim.x * PLAN_THREADS) P.sink.grad_verts[k] = 0.0f;
     }
@@ -442,18 +462,24 @@ __global__ __launch_bounds__(PLAN_THREADS) void k_edge_plan(const BwdParams P)
     uint32_t wave_base = block_base;
     for (int w = 0; w < wave; w++) wave_base += wave_sum[w];
     if (i >= total) return;
+    // (k_edge_segments finds a face's chunks by their records: only the faces of the serial fallback are noted, as a list)
+    const bool per_face = !segment_path(P);
     if (!contributes) {
-        P.chunk_base[i] = -2;
+        if (per_face) P.chunk_base[i] = -2;
         return;
     }
     const uint32_t base = wave_base + incl - nchunks;
     if (base + nchunks > P.cap) {
-        P.chunk_base[i] = -1;  // no room: k_edge_reduce walks this face serially
+        // no room: k_edge_reduce / k_edge_segments walks this face serially
+        if (per_face)
+            P.chunk_base[i] = -1;
+        else
+            P.chunk_base[atomicAdd(P.counter + 1, 1u)] = (int32_t)i;
         // the slots it reserved below the cap must not look like valid work to the scan kernels (face id out of range)
         for (uint32_t c = base; c < P.cap; c++) P.chunk_desc[c] = make_uint4(0xffffffffu, 0xffffffffu, 0u, 0u);
         return;
     }
-    P.chunk_base[i] = (int32_t)base;
+    if (per_face) P.chunk_base[i] = (int32_t)base;
     uint32_t c = base;
 #pragma unroll
     for (int e = 0; e < 6; e++) {
@@ -828,16 +854,9 @@ __global__ __launch_bounds__(256) void k_edge_rows(const BwdParams P, int nrows)
     }
 }
 
-// chunk_out[c] += the "out" scans of chunk c's edge pixels, in lane order: one thread per chunk, its 8 result slots are one
-// 64-byte line (k_edge_reduce, one thread per FACE, would chase them one dependent load at a time: 32 -> 123 us).
-__global__ __launch_bounds__(256) void k_chunk_sum(const BwdParams P)
+// a + the "out" scans of chunk c's edge pixels (mask m != 0: which of them own one), in lane order
+__device__ __forceinline__ float2 chunk_add_owners(const BwdParams& P, uint32_t c, uint32_t m, float2 a)
 {
-    const uint32_t nchunks = min(*P.counter, P.cap);
-    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
-    if (c >= nchunks) return;
-    uint32_t m = P.chunk_mask[c];
-    if (!m) return;
-    float2 a = P.chunk_out[c];
     const float4* q = reinterpret_cast<const float4*>(P.own_out + (size_t)c * CHUNK);
 #pragma unroll
     for (int h = 0; h < CHUNK / 2; h++) {
@@ -852,7 +871,38 @@ __global__ __launch_bounds__(256) void k_chunk_sum(const BwdParams P)
             a.y += v.w;
         }
     }
-    P.chunk_out[c] = a;
+    return a;
+}
+
+// chunk_out[c] += the "out" scans of chunk c's edge pixels, in lane order: one thread per chunk, its 8 result slots are one
+// 64-byte line (k_edge_reduce, one thread per FACE, would chase them one dependent load at a time: 32 -> 123 us).
+__global__ __launch_bounds__(256) void k_chunk_sum(const BwdParams P)
+{
+    const uint32_t nchunks = min(*P.counter, P.cap);
+    const uint32_t c = blockIdx.x * 256u + threadIdx.x;
+    if (c >= nchunks) return;
+    uint32_t m = P.chunk_mask[c];
+    if (!m) return;
+    P.chunk_out[c] = chunk_add_owners(P, c, m, P.chunk_out[c]);
+}
+
+// One face's gradient row onto its three vertices (the vertex sink), zeros skipped.
+__device__ __forceinline__ void sink_add_face(const BwdParams& P, long i, const float grad_face[9])
+{
+    bool any = false;
+#pragma unroll
+    for (int k = 0; k < 9; k++) any = any || grad_face[k] != 0.0f;
+    if (!any) return;
+    const int bn = (int)(i / P.nf), fn = (int)(i % P.nf);
+    const bool twin = P.sink.fill_back && fn >= P.sink.nf0;
+    const int32_t* idx = P.sink.faces_idx + (size_t)bn * P.sink.fstride + (size_t)(twin ? fn - P.sink.nf0 : fn) * 3;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float* dst = P.sink.grad_verts + ((size_t)bn * P.sink.nv + idx[twin ? 2 - k : k]) * 3;
+#pragma unroll
+        for (int d = 0; d < 3; d++)
+            if (grad_face[3 * k + d] != 0.0f) unsafeAtomicAdd(&dst[d], grad_face[3 * k + d]);
+    }
 }
 
 __global__ __launch_bounds__(256) void k_edge_reduce(const BwdParams P)
@@ -910,20 +960,7 @@ __global__ __launch_bounds__(256) void k_edge_reduce(const BwdParams P)
     }
     if (P.sink.grad_verts) {
         if (base == -2) return;   // (hidden, back-facing or without an edge pixel: every term is zero)
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < 9; k++) any = any || grad_face[k] != 0.0f;
-        if (!any) return;
-        const int bn = (int)(i / P.nf), fn = (int)(i % P.nf);
-        const bool twin = P.sink.fill_back && fn >= P.sink.nf0;
-        const int32_t* idx = P.sink.faces_idx + (size_t)bn * P.sink.fstride + (size_t)(twin ? fn - P.sink.nf0 : fn) * 3;
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float* dst = P.sink.grad_verts + ((size_t)bn * P.sink.nv + idx[twin ? 2 - k : k]) * 3;
-#pragma unroll
-            for (int d = 0; d < 3; d++)
-                if (grad_face[3 * k + d] != 0.0f) unsafeAtomicAdd(&dst[d], grad_face[3 * k + d]);
-        }
+        sink_add_face(P, i, grad_face);
         return;
     }
     if (accumulate) {
@@ -933,6 +970,135 @@ __global__ __launch_bounds__(256) void k_edge_reduce(const BwdParams P)
 #pragma unroll
         for (int k = 0; k < 9; k++) P.grad_faces[i * 9 + k] = grad_face[k];
     }
+}
+
+// The frame step's k_chunk_sum + k_edge_reduce in one launch, one thread per CHUNK SLOT instead of one per face.  k_edge_plan
+// writes a face's records side by side in (edge, axis) order, so the chunks of one (face, edge, axis) walk are a run of slots
+// with equal {face, e}: a SEGMENT.  Every lane forms its chunk's value (k_chunk_sum's expression: coalesced, all in parallel);
+// the lane of a segment's first chunk -- its head -- then adds the segment's values in chunk order from 0.f, which is the
+// sum k_edge_reduce formed for that walk, and adds the two results to the edge's end points pi0 = e >> 1, pi1 = (pi0 + 1) % 3,
+// coordinate 1 - axis.  The values come by lane shuffles; for a segment that runs on past the wave's last lane (a face hundreds
+// of pixels long) the wave fetches the following slots 64 at a time as well.
+// Nothing here depends on the faces' coordinates, on `visible` or on `chunk_base`.
+// The first SEG_SERIAL_BLOCKS workgroups walk the faces whose chunks found no room (k_edge_plan's list) pixel by pixel.
+constexpr int SEG_SERIAL_BLOCKS = 8;
+
+__device__ __forceinline__ void segment_add(const BwdParams& P, long i, int e, float a0, float a1)
+{
+    if (a0 == 0.0f && a1 == 0.0f) return;
+    const int bn = (int)(i / P.nf), fn = (int)(i % P.nf);
+    const int axis = e & 1, pi0 = e >> 1, pi1 = (pi0 + 1) % 3;
+    const bool twin = P.sink.fill_back && fn >= P.sink.nf0;
+    const int32_t* idx = P.sink.faces_idx + (size_t)bn * P.sink.fstride + (size_t)(twin ? fn - P.sink.nf0 : fn) * 3;
+    float* g = P.sink.grad_verts + (size_t)bn * P.sink.nv * 3 + (1 - axis);
+    if (a0 != 0.0f) unsafeAtomicAdd(&g[(size_t)idx[twin ? 2 - pi0 : pi0] * 3], a0);
+    if (a1 != 0.0f) unsafeAtomicAdd(&g[(size_t)idx[twin ? 2 - pi1 : pi1] * 3], a1);
+}
+
+__global__ __launch_bounds__(256) void k_edge_segments(const BwdParams P)
+{
+    const int lane = threadIdx.x & 63;
+    if (blockIdx.x < SEG_SERIAL_BLOCKS) {
+        // serial fallback: one face per thread, k_edge_reduce's walk (the literal reference order: every term is subtracted
+        // straight from the face's row); consecutive list entries go to different waves
+        const uint32_t n = P.counter[1];
+        constexpr uint32_t WAVES = SEG_SERIAL_BLOCKS * 4;
+        const uint32_t wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+        const bool use_alpha = (P.flags & SDN_ALPHA) != 0, use_rgb = (P.flags & SDN_RGB) != 0;
+        const float is_f = (float)P.S;
+        for (uint32_t k = (uint32_t)lane * WAVES + wave; k < n; k += 64u * WAVES) {
+            const long i = P.chunk_base[k];
+            const int bn = (int)(i / P.nf), fn = (int)(i % P.nf);
+            float face[9];
+#pragma unroll
+            for (int j = 0; j < 9; j++) face[j] = P.faces[i * 9 + j];
+            const MapReader M(P, bn);
+            float grad_face[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+            for (int e = 0; e < 6; e++) {
+                const int axis = e & 1;
+                const EdgeWalk w = edge_walk(face, e >> 1, axis, is_f);
+                for (int d0 = w.d0_from; d0 <= w.d0_to; d0++)
+                    edge_pixel(P, M, w, fn, axis, d0, use_alpha, use_rgb, 0, 1, grad_face[w.pi0 * 3 + (1 - axis)],
+                               grad_face[w.pi1 * 3 + (1 - axis)]);
+            }
+            sink_add_face(P, i, grad_face);
+        }
+        return;
+    }
+    const uint32_t nchunks = min(*P.counter, P.cap);
+    const uint32_t c = (blockIdx.x - (uint32_t)SEG_SERIAL_BLOCKS) * 256u + threadIdx.x;
+    const uint32_t c_wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(c - (uint32_t)lane));
+    if (c_wave >= nchunks) return;   // (the whole wave)
+    const uint32_t total = (uint32_t)((long)P.bs * P.nf);
+    // a slot's record, its "in" sums and its owner mask, requested together (an invalid slot -- reserved by a face that then
+    // fell back to serial -- holds zeros in the latter two: k_edge_scan_sil)
+    auto key_at = [&](uint32_t s) { return *reinterpret_cast<const uint2*>(P.chunk_desc + s); };
+    uint2 d = make_uint2(0xffffffffu, 0xffffffffu);
+    float2 v = make_float2(0.f, 0.f);
+    uint32_t m = 0u;
+    if (c < nchunks) {
+        d = key_at(c);
+        v = P.chunk_out[c];
+        m = P.chunk_mask[c];
+    }
+    // the records on either side of the wave's 64 slots (wave-uniform addresses)
+    uint2 before = make_uint2(0xffffffffu, 0xffffffffu), after = before;
+    if (c_wave > 0u) before = key_at(c_wave - 1u);
+    if (c_wave + 64u < nchunks) after = key_at(c_wave + 64u);
+    const bool valid = d.x < total;
+    if (valid && m) v = chunk_add_owners(P, c, m, v);
+    // a head: the slot before it holds another (face, e)
+    uint32_t px = __shfl_up(d.x, 1, 64), py = __shfl_up(d.y, 1, 64);
+    if (lane == 0) {
+        px = before.x;
+        py = before.y;
+    }
+    const bool head = valid && (px != d.x || py != d.y);
+    // the segment's chunks inside this wave: up to the next head or invalid slot
+    const unsigned long long bounds = __ballot(head || !valid);
+    const unsigned long long above = lane == 63 ? 0ull : bounds >> (lane + 1);
+    const int len = head ? (above ? __ffsll((long long)above) : 64 - lane) : 0;
+    float a0 = 0.f, a1 = 0.f;
+    for (int k = 0; __ballot(k < len) != 0ull; k++) {
+        const float tx = __shfl(v.x, lane + k, 64), ty = __shfl(v.y, lane + k, 64);
+        if (k < len) {
+            a0 += tx;
+            a1 += ty;
+        }
+    }
+    // The wave's last segment may run on in the slots after it (a walk of hundreds of pixels: the panels of a CAD mesh).  Then
+    // the WHOLE wave fetches the next 64 chunks' values the same way and the head adds those of its segment in slot order,
+    // until a round meets the segment's end.
+    const unsigned long long runs_on = __ballot(head && !above && after.x == d.x && after.y == d.y);
+    if (runs_on) {   // (at most one lane)
+        const int hl = __ffsll((long long)runs_on) - 1;
+        const uint32_t kx = (uint32_t)__builtin_amdgcn_readlane((int)d.x, hl), ky = (uint32_t)__builtin_amdgcn_readlane((int)d.y, hl);
+        for (uint32_t s0 = c_wave + 64u; s0 < nchunks; s0 += 64u) {
+            const uint32_t s = s0 + (uint32_t)lane;
+            uint2 ds = make_uint2(0xffffffffu, 0xffffffffu);
+            float2 vs = make_float2(0.f, 0.f);
+            uint32_t ms = 0u;
+            if (s < nchunks) {
+                ds = key_at(s);
+                vs = P.chunk_out[s];
+                ms = P.chunk_mask[s];
+            }
+            const bool mine = ds.x == kx && ds.y == ky;
+            if (mine && ms) vs = chunk_add_owners(P, s, ms, vs);
+            const unsigned long long others = ~__ballot(mine);
+            const int n = others ? __ffsll((long long)others) - 1 : 64;   // (the segment's slots are contiguous)
+            for (int k = 0; k < n; k++) {
+                const float tx = __shfl(vs.x, k, 64), ty = __shfl(vs.y, k, 64);
+                if (lane == hl) {
+                    a0 += tx;
+                    a1 += ty;
+                }
+            }
+            if (n < 64) break;
+        }
+    }
+    if (!head) return;
+    segment_add(P, (long)d.x, (int)d.y, a0, a1);
 }
 
 __global__ __launch_bounds__(256) void k_bwd_pixels(const BwdParams P)
@@ -1183,14 +1349,20 @@ int sdn::rasterize_bwd_core(const VertexSink* sink, const float* faces, const fl
                 hipLaunchKernelGGL(k_edge_scan_sil, dim3(256 * 8), dim3(256), 0, st, P);
                 const int nrows = 2 * bs * S;
                 hipLaunchKernelGGL(k_edge_rows, dim3((unsigned)nrows), dim3(256), (size_t)S * sizeof(float2), st, P, nrows);
-                hipLaunchKernelGGL(k_chunk_sum, dim3(cdiv((long)cap, 256)), dim3(256), 0, st, P);
+                if (!segment_path(P)) hipLaunchKernelGGL(k_chunk_sum, dim3(cdiv((long)cap, 256)), dim3(256), 0, st, P);
             } else
                 hipLaunchKernelGGL(k_edge_scan, dim3(256 * 8), dim3(256), 0, st, P);
         }
         if ((rc = check_launch("k_edge_scan"))) return rc;
     }
-    hipLaunchKernelGGL(k_edge_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, P);
-    if ((rc = check_launch("k_edge_reduce"))) return rc;
+    if (segment_path(P)) {
+        // (outside the TIME_EDGE_SCAN region, as k_edge_reduce is: the region is scan + rows on this path)
+        hipLaunchKernelGGL(k_edge_segments, dim3((unsigned)(cdiv((long)cap, 256) + SEG_SERIAL_BLOCKS)), dim3(256), 0, st, P);
+        if ((rc = check_launch("k_edge_segments"))) return rc;
+    } else {
+        hipLaunchKernelGGL(k_edge_reduce, dim3(cdiv(total, 256)), dim3(256), 0, st, P);
+        if ((rc = check_launch("k_edge_reduce"))) return rc;
+    }
 
     const bool need_tex = (P.flags & SDN_RGB) && grad_textures;
     if (need_tex && !(flags & SDN_ACCUMULATE)) {

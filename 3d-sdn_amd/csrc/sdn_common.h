@@ -74,7 +74,8 @@ int rasterize_fwd_core(const FaceSource* src, const float* faces, const float* t
                        float* alpha_out, float* depth_out, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 // sdn_rasterize_bwd whose edge pass adds each face's gradient straight to its vertices (r06, sdn_render_maps_bwd's silhouette-only
-// case): k_edge_plan clears grad_verts [bs, nv, 3] on its way, k_edge_reduce scatters with float atomics -- the [bs, nf, 3, 3] face
+// case): k_edge_plan clears grad_verts [bs, nv, 3] on its way, k_edge_segments (k_edge_reduce without the silhouette fast path) scatters
+// with float atomics -- the [bs, nf, 3, 3] face
 // gradient, its gather launch and the clearing memset are gone.  Only for passes without colour / depth terms.
 struct VertexSink {
     const int32_t* faces_idx;   // [1 | bs, nf0, 3]
