@@ -15,11 +15,13 @@
 //   k_raster_tiles one 256-thread workgroup per 32x32-pixel tile (framebuffer bin in LDS: 1024 x u64 =
 //                  8 KiB).  The tile reads its own face list (coalesced 4-byte indices; if the lists of a
 //                  batch element overflow their budget the tile streams the 4-byte tile-box of every face
-//                  instead) in four runs, one per wave.  A wave rasterises 64 faces at a time: small faces (a few
-//                  pixels: nearly all of an 85k-face mesh) stay with their lane(s), which only run the edge tests and
-//                  queue the covered pixels in LDS; every 64 queued hits are shaded by all 64 lanes (barycentrics,
+//                  instead) in four runs, one per wave.  A wave rasterises 64 faces at a time, one fetched per lane: the
+//                  clipped candidate boxes of up to 256 pixels (nearly all of an 85k-face mesh: a few pixels each) form ONE
+//                  stream of (face, pixel) candidates, of which every pass of the wave takes 64 consecutive ones whichever
+//                  faces they belong to (the owner's coordinates come through ds_bpermute); a pass only runs the edge tests and
+//                  queues the covered pixels in LDS; every 64 queued hits are shaded by all 64 lanes (barycentrics,
 //                  perspective depth) and resolved with ds_min_u64 on the packed key ord(depth) << 32 | face_index;
-//                  large faces are broadcast (v_readlane) and shared by the wave.  r02: 658 -> 399 us per 16-object frame.
+//                  larger faces are broadcast (v_readlane) and walked by row spans.  r02: 658 -> 399 us per 16-object frame.
 //                  The epilogue recomputes the winner's barycentrics, samples colours
 //                  (rasterize.py:398-423), blends the background, flips vertically and 2x2-averages
 //                  (rasterize.py:951-966) straight from LDS to the output maps.
@@ -46,16 +48,16 @@ constexpr int NWAVE = NTHR / 64;
 static_assert(NTHR % 64 == 0 && NTHR >= 2 * TS && TS <= 32, "tile / workgroup geometry (hit queue packs px, py in 5 bits)");
 constexpr int QCAP = 512;   // queued faces per flush (<= 255 carried + 256 new)
 constexpr int FREC = 13;        // floats per face record of a batch (odd: consecutive records start in different LDS banks)
-#ifndef SDN_LAB_SMALL_AREA
-#define SDN_LAB_SMALL_AREA 32   // (sweep r03, us per frame car_like / cad_like: 12: 208/303, 24: 191/297, 32: 185/293, 48: 193/306, 64: 200/318, 96: 214/323)
+#ifndef SDN_LAB_FLAT_MAX
+#define SDN_LAB_FLAT_MAX 256   // (sweep, k_raster_tiles us per launch, two runs each, cad_like: the lane-private + linear wave-shared walks this replaced
+                               // 255.3 / 256.2; 32: 252.1 / 250.3, 64: 249.2 / 241.8, 128: 245.1 / 242.9, 256: 241.4 / 240.2; car_like: 191.4 / 192.2; 32: 188.6 /
+                               // 189.9, 256: 172.2 / 174.3 -- taken while boxes between this value and 256 pixels still had the linear wave-shared walk;
+                               // profiles/raster_flat_walk.md.  The row-span threshold it now also is, swept as SDN_LAB_SPAN_AREA: r04, car_like / cad_like:
+                               // 0: 219/312, 128: 203/291, 256: 200/290, 512: 200/289, off: 200/299; r06, with the depth cull, car_like / cad_like / the six
+                               // templates / 3776e4d1: 64: 196/262/296/489, 128: 191/261/294/470, 256: 189/253/287/446, 512: 189/255/326/512, 1024: 187/260/487/-)
 #endif
-constexpr int SMALL_AREA = SDN_LAB_SMALL_AREA;  // clipped candidate boxes up to this many pixels are rasterised by ONE lane
-#ifndef SDN_LAB_SPAN_AREA
-#define SDN_LAB_SPAN_AREA 256   // (sweep r04, us per launch car_like / cad_like: 0: 219/312, 128: 203/291, 256: 200/290, 512: 200/289, off: 200/299;
-                                // r06, with the depth cull, car_like / cad_like / the six templates / 3776e4d1: 64: 196/262/296/489, 128: 191/261/294/470,
-                                // 256: 189/253/287/446, 512: 189/255/326/512, 1024: 187/260/487/-)
-#endif
-constexpr int SPAN_AREA = SDN_LAB_SPAN_AREA;    // wave-shared boxes above this many pixels are walked by row spans
+constexpr int FLAT_MAX = SDN_LAB_FLAT_MAX;  // clipped candidate boxes up to this many pixels join the batch's candidate stream; larger ones are walked by row spans
+static_assert(FLAT_MAX >= 1 && FLAT_MAX <= 256, "a batch's stream holds at most 64 * 256 candidates: 14 bits of start, at most 256 passes (the marks are u16, 0xffff = none)");
 #ifndef SDN_LAB_HIZ_MIN_LIST
 #define SDN_LAB_HIZ_MIN_LIST 257   // = every tile on the long-list path (> 64 * NWAVE entries); us per launch cad_like / real templates / car_like:
                                    // off 289 / 490 / 196, always 291 / 325 / 214, >= 2048: 290 / 490 / 196, 1024: 288 / 343 / 195, 512: 275 / 317 / 195, 256: 266 / 313 / 196
@@ -705,10 +707,10 @@ __device__ __forceinline__ bool hiz_hidden(const uint32_t* blockmax, const uint3
 // batches, and a block only closes when all 64 of its pixels are covered -- near silhouettes and between parts they never are;
 // the per-pixel `behind` test already catches 62 % of the passing candidates at the price of one LDS read.
 template <bool COUNT, int HIZ>
-__global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
+__global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   // (6 waves per SIMD: at most 80 registers)
 {
     unsigned n_cand = 0, n_in = 0, n_key = 0;
-    // COUNT build: constant-clock ticks (wall_clock64: 100 MHz) this wave spent per phase (batch fetch, lane-private boxes, wave-shared boxes, thin
+    // COUNT build: constant-clock ticks (wall_clock64: 100 MHz) this wave spent per phase (batch fetch, the candidate stream [the slot of the former lane-private boxes], wave-shared row spans, thin
     // faces, epilogue) and the workgroup's total; summed / maximised over the launch into counters[3..]
     unsigned long long c_fetch = 0, c_small = 0, c_large = 0, c_thin = 0, c_epi = 0, t_mark = 0, t_begin = 0;
     auto tick = [&](unsigned long long& acc) {
@@ -726,6 +728,7 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
     __shared__ uint32_t hit_queue[NWAVE][128];       // per wave: (face slot | px << 6 | py << 11) of pixels that passed the edge tests
     __shared__ float face_rec[NWAVE][64 * FREC];     // per wave: the current batch's z0 z1 z2, inverse matrix, face index
     __shared__ uint32_t blockmax[(TS / 8) * (TS / 8)];   // HIZ: per 8 x 8 block an upper bound of its winners' depth keys
+    __shared__ uint32_t own_strip[NWAVE][32];        // per wave: 64 x u16, the number of the latest pass in which a face's candidates started at each position
     static_assert(TS == 32, "the hi-z refresh maps 64 lanes x 16 reads onto a 32 x 32 tile");
 
     const int tid = threadIdx.x;
@@ -767,13 +770,17 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
 
     // A wave takes 64 faces per batch: every lane first fetches ONE face of the batch (index, candidate box, 9 coordinates,
     // 9 inverse-matrix entries -- all loads of the batch are in flight together) and clips its box to the tile.
-    //   * faces whose clipped box holds <= SMALL_AREA pixel centres (nearly all faces of an 85k-face mesh: a few pixels
-    //     each) stay with their lane: 64 faces are rasterised at once, each lane walking its own box.  The previous
-    //     one-face-per-wave scheme spent ~150 instructions per face to test ~20 pixels with a third of the lanes;
-    //   * larger faces are broadcast with v_readlane and the 64 lanes share their pixels, as before.
-    // A (face, pixel) pair is evaluated by the same float operations on either path and visibility is an atomicMin on
-    // (depth, face) keys, so the split cannot change the result.  LDS traffic: 2 coordinate-table reads per candidate
-    // pixel and the ds_min_u64 of pixels that are actually covered.
+    //   * faces whose clipped box holds <= FLAT_MAX pixel centres join the batch's candidate stream: an exclusive prefix sum of
+    //     the box areas gives every face its start, and pass p of the wave tests the candidates 64 p .. 64 p + 63, lane by lane,
+    //     whichever faces own them.  Every pass but the batch's last is full and the loop is as long as the SUM of the areas
+    //     over 64.  (Before: one lane per small face, looping to the largest box of the 64 with a quarter of the lanes busy, and
+    //     one broadcast + ceil(area / 64) passes, the last half empty, per medium box: 256 -> 245 us per launch on cad_like,
+    //     189 -> 171 on car_like, profiles/raster_flat_walk.md);
+    //   * larger faces are broadcast with v_readlane and the 64 lanes share their pixels by row spans.
+    // A (face, pixel) pair is evaluated by the same float operations on either path -- the stream MOVES the owner's operands
+    // to the candidate's lane, it does not recompute them -- and visibility is an atomicMin on (depth, face) keys, so the
+    // split cannot change the result.  LDS traffic: per pass one mark, one read and ten permutes for the owner, per
+    // candidate 2 coordinate-table reads and the ds_min_u64 of pixels that are actually covered.
     auto shade_hit = [&](const float z0, const float z1, const float z2, const float (&inv)[9], const uint32_t qf,
                          const int px, const int py) {
         float bw[3];
@@ -833,18 +840,13 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
             }
         }
     };
-    // ids[0..n), 1 <= n <= 64; called by a whole wave.  With fewer than 33 faces the wave gives each face k = 2^kshift
-    // lanes (k * n <= 64) that interleave its pixels: a tile's ~100 list entries split over 4 waves leave ~25 faces per
-    // wave, and the loop length is the largest box of the batch, not the number of faces.
+    // ids[0..n), 1 <= n <= 64; called by a whole wave: lane l fetches face ids[l] (slot = lane).
     auto raster_batch = [&](const uint32_t* ids, const int n) {
         if constexpr (HIZ > 0) {
             if (HIZ == 1 || hiz_on) refresh_hiz();
         }
-        const int kshift = 31 - __clz(64 / n);
-        const int k = 1 << kshift;
-        const int q = lane >> kshift, sub = lane & (k - 1);
-        const bool mine = q < n;
-        const uint32_t qf_l = mine ? ids[q] : 0u;
+        const bool mine = lane < n;
+        const uint32_t qf_l = mine ? ids[lane] : 0u;
         uint4 pb_l = make_uint4(0u, 0u, 0u, 0u);
         float f_l[9], inv_l[9];
 #pragma unroll
@@ -868,8 +870,8 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
                 area_l = 0;
         }
         // the batch's face records for the shading lanes (the previous batch's hits were drained before returning)
-        if (mine && sub == 0) {
-            float* r = frec + q * FREC;
+        if (mine) {
+            float* r = frec + lane * FREC;
             r[0] = f_l[2];
             r[1] = f_l[5];
             r[2] = f_l[8];
@@ -882,24 +884,77 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
             asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
             tick(c_fetch);
         }
-        // ---- small faces: k lanes each, test only
+        unsigned long long big = __ballot(area_l > FLAT_MAX);
+        // ---- the candidate stream: boxes of up to FLAT_MAX pixels, 64 consecutive (face, pixel) candidates per pass.  A candidate
+        // finds its owner by COUNTING: faces in lane order are the stream's faces in start order, so the owner's rank among the
+        // faces of the stream is the number of starts at or below the candidate, less one.  Per pass the faces that start in it
+        // mark their start position in a 64-entry LDS strip, every lane reads its own entry, and one ballot + v_mbcnt turn the
+        // marks into ranks (14 instructions in the ISA; a first cut that stored slot numbers in the strip, cleared it every pass and
+        // looked for the highest mark at or below the lane took 30 and measured 245 / 246 us where this takes 241 / 240).  The
+        // owner's six x / y coordinates, packed box, 1 / width and depth bound come through ds_bpermute, issued by all 64 lanes
+        // before the pass diverges; the edge differences of inside_ndc are recomputed per candidate (6 v_sub: as many
+        // instructions as 6 more permutes, and the same floats).  A pass is about 66 vector-ALU and 15 LDS instructions in the ISA (the
+        // ten permutes, mark, read, two table reads, the depth read), queue append included; the linear wave-shared walk was ~45 per pass
+        // plus ~40 per box.
         {
-            const bool small = area_l > 0 && area_l <= SMALL_AREA * k;
-            const float rw = 1.0f / (float)(lw > 0 ? lw : 1);
-            for (int i = sub; __ballot(small && i < area_l) != 0ull; i += k) {
+            const int fa = area_l <= FLAT_MAX ? area_l : 0;
+            int incl = fa;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const int o = __shfl_up(incl, d, 64);
+                if (lane >= d) incl += o;
+            }
+            const int T = __builtin_amdgcn_readlane(incl, 63);
+            // what a candidate needs of its owner besides the six coordinates: box origin and width (tile pixels), stream start
+            // (< 64 * 256: 14 bits; the sign bit marks a lane without candidates); 1 / width
+            const int box_l = ((lx0 - X0) & 31) | (((ly0 - Y0) & 31) << 5) | (((lw - 1) & 31) << 10) | ((incl - fa) << 15) |
+                              (fa > 0 ? 0 : (int)0x80000000);
+            const float rw_l = 1.0f / (float)(lw > 0 ? lw : 1);
+            // the flat faces in lane order are the stream's faces in start order: rank r's lane (the other lanes fill the ranks behind)
+            const unsigned long long fm = __ballot(fa > 0);
+            const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
+            const int rank_l = fa > 0 ? below : (int)__popcll(fm) + lane - below;
+            const int lane_of_rank = __builtin_amdgcn_ds_permute(rank_l << 2, lane);
+            uint32_t* strip = own_strip[wave];
+            uint16_t* strip16 = reinterpret_cast<uint16_t*>(strip);
+            if (lane < 32) strip[lane] = 0xffffffffu;   // (pass numbers stay below 64 * 256 / 64 = 256)
+            __builtin_amdgcn_wave_barrier();
+            int rank0 = -1;   // (wave-uniform) rank of the face that owns the last candidate of the previous pass
+            for (int base = 0, pass = 0; base < T; base += 64, pass++) {
+                // owner look-up: the faces that START inside this pass mark their start with the pass number; a candidate belongs
+                // to the face of rank (starts before this pass) + (starts at or below its position) - 1
+                const int rel = (box_l >> 15) - base;
+                if ((unsigned)rel < 64u) strip16[rel] = (uint16_t)pass;
+                __builtin_amdgcn_wave_barrier();
+                const bool starts = (int)strip16[lane] == pass;
+                __builtin_amdgcn_wave_barrier();
+                const unsigned long long sm = __ballot(starts);
+                const int rk = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(sm >> 32),
+                                                              __builtin_amdgcn_mbcnt_lo((uint32_t)sm, (uint32_t)(rank0 + (starts ? 1 : 0))));
+                rank0 += (int)__popcll(sm);
+                const int s = __builtin_amdgcn_ds_bpermute(rk << 2, lane_of_rank);
+                const int a4 = s << 2;
+                const int box = __builtin_amdgcn_ds_bpermute(a4, box_l);
+                const float rw = __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(rw_l)));
+                const uint32_t zc = (uint32_t)__builtin_amdgcn_ds_bpermute(a4, (int)zc_l);
+                float f[9];
+#pragma unroll
+                for (int kk = 0; kk < 9; kk++)
+                    f[kk] = (kk % 3 == 2) ? 0.0f : __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(f_l[kk])));
                 bool hit = false;
                 int px = 0, py = 0;
-                if (small && i < area_l) {
+                if (base + lane < T) {
+                    const int i = base + lane - (box >> 15);
                     const int yy = (int)(((float)i + 0.5f) * rw);
-                    const int xx = i - yy * lw;
-                    px = lx0 - X0 + xx;
-                    py = ly0 - Y0 + yy;
+                    const int xx = i - yy * (((box >> 10) & 31) + 1);
+                    px = (box & 31) + xx;
+                    py = ((box >> 5) & 31) + yy;
                     if constexpr (COUNT) n_cand++;
-                    hit = inside_ndc(f_l, xtab[px], ytab[py]);
+                    hit = inside_ndc(f, xtab[px], ytab[py]);
                     if constexpr (COUNT) n_in += hit ? 1u : 0u;
-                    if (hit) hit = !behind(zc_l, px, py);
+                    if (hit) hit = !behind(zc, px, py);
                 }
-                push_hits(hit, (uint32_t)q | ((uint32_t)px << 6) | ((uint32_t)py << 11));
+                push_hits(hit, (uint32_t)s | ((uint32_t)px << 6) | ((uint32_t)py << 11));
             }
         }
         tick(c_small);
@@ -912,51 +967,25 @@ __global__ __launch_bounds__(NTHR) void k_raster_tiles(const FwdParams P)
         // interleave over the span.  A superset of the passing pixels is tested with the exact predicate, as before; what
         // changes is how many fail: a long thin diagonal triangle fills a few percent of its box (CAD meshes: 27 % of all
         // candidate tests passed, 83 % of the candidates came from this path).
-        unsigned long long big = __ballot(area_l > SMALL_AREA * k && sub == 0);
         const float fS = (float)S, fS1 = (float)(S - 1);
         while (big) {
             const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)big) - 1);
             big &= big - 1ull;
-            const int x0 = __builtin_amdgcn_readlane(lx0, j), y0 = __builtin_amdgcn_readlane(ly0, j);
-            const int w = __builtin_amdgcn_readlane(lw, j), h = __builtin_amdgcn_readlane(lh, j);
+            // (the clipped box again, from the packed one, in scalar registers)
+            const uint32_t pbx_j = (uint32_t)__builtin_amdgcn_readlane((int)pb_l.x, j), pby_j = (uint32_t)__builtin_amdgcn_readlane((int)pb_l.y, j);
+            const int x0 = max((int)(pbx_j & 0xffffu), X0), y0 = max((int)(pby_j & 0xffffu), Y0);
+            const int w = min((int)(pbx_j >> 16), X0 + TS - 1) - x0 + 1, h = min((int)(pby_j >> 16), Y0 + TS - 1) - y0 + 1;
             const uint32_t zc = (uint32_t)__builtin_amdgcn_readlane((int)zc_l, j);
             const float mj = __int_as_float(__builtin_amdgcn_readlane((int)pb_l.z, j));
-            const uint32_t slot = (uint32_t)(j >> kshift);
+            const uint32_t slot = (uint32_t)j;
             float f[9];
 #pragma unroll
             for (int kk = 0; kk < 9; kk++) f[kk] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(f_l[kk]), j));
-            if (w * h <= SPAN_AREA) {
-                // a box of a few passes: the span set-up (~50 instructions) and its rows-to-lanes rounding cost more than
-                // the failed tests it would save (measured: spans for every large face made the launch 4-10 % longer)
-                const int area = w * h;
-                // (Measured and dropped, r06: AXIS-ALIGNED passes -- a lane keeps one column (or row) of the box for the whole face,
-                // so that its coordinate, one factor pair of each edge test, its zbuf address and queue entry are computed once per
-                // face and a pass of 64 / 2^ceil(log2 w) rows only evaluates three subtract-multiply-compare triples: ~25 vector
-                // instructions per pass in the ISA against ~45 of the linear walk below, taken when a box side fills >= 5/8 of its
-                // power of two.  Bit-identical maps, and NOT faster: cad_like 288.6 vs 286.1 us, car_like 204.1 vs 197.5, the real
-                // templates 520 vs 490 (mixed frame) and 699 vs 654 us (mesh 3776e4d1); fill thresholds 4/8 .. 7/8 within 2 % of each
-                // other (profiles/r06c_raster_sweep2.log; the first cut with the orientation as a run-time select was 10 % slower,
-                // r06c_raster_sweep.log).  The idle lanes of partly filled passes and the extra passes cost what the shorter
-                // passes save: the walk is not bound by the instructions of the predicate.)
-                const float rw = 1.0f / (float)w;
-                for (int i0 = 0; i0 < area; i0 += 64) {
-                    const int i = i0 + lane;
-                    bool hit = false;
-                    int px = 0, py = 0;
-                    if (i < area) {
-                        const int yy = (int)(((float)i + 0.5f) * rw);
-                        const int xx = i - yy * w;
-                        px = x0 - X0 + xx;
-                        py = y0 - Y0 + yy;
-                        if constexpr (COUNT) n_cand++;
-                        hit = inside_ndc(f, xtab[px], ytab[py]);
-                        if constexpr (COUNT) n_in += hit ? 1u : 0u;
-                        if (hit) hit = !behind(zc, px, py);
-                    }
-                    push_hits(hit, slot | ((uint32_t)px << 6) | ((uint32_t)py << 11));
-                }
-                continue;
-            }
+            // (Measured and dropped, r06, on the linear walk that boxes of a few passes had before they joined the stream: AXIS-ALIGNED
+            // passes -- a lane keeps one column (or row) of the box for the whole face: ~25 vector instructions per pass in the ISA
+            // against ~45, bit-identical maps, and NOT faster: cad_like 288.6 vs 286.1 us, car_like 204.1 vs 197.5, the real templates
+            // 520 vs 490 and 699 vs 654 us; profiles/r06c_raster_sweep2.log.  Row spans for EVERY shared box: 4-10 % longer, the span
+            // set-up of ~50 instructions and its rows-to-lanes rounding cost more than the failed tests they save on a small box.)
             const int hs = h > 1 ? 32 - __clz(h - 1) : 0;          // ceil(log2 h) <= 5
             const int rshift = 6 - hs, per_row = 1 << rshift;      // lanes per row: 2 .. 64
             const int row = lane >> rshift, rsub = lane & (per_row - 1);
