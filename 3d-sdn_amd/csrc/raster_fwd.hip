@@ -29,9 +29,10 @@
 // Exactness: a (face, pixel) pair is evaluated with the same float operations wherever it is
 // evaluated, so binning cannot change the result as long as no covering pair is skipped.  The
 // bounding box is therefore dilated by a proven bound on where rounding can make the NDC edge
-// tests of rasterize.py:311-313 pass (see face_margin_px); degenerate faces fall back to the whole
-// screen band around the line through their longest edge, which is where the reference's unbounded edge
-// tests can still accept pixels.
+// tests of rasterize.py:311-313 pass (see face_margin_px); slivers whose bound is large are tested in a
+// band around the line through their longest edge, inside their dilated box; degenerate faces without a
+// bound take that band across the whole screen, which is where the reference's unbounded edge tests can
+// still accept pixels; faces with a repeated vertex cannot record a pixel and are dropped (k_face_setup).
 #include <mutex>
 #include <type_traits>
 #include <vector>
@@ -81,13 +82,14 @@ struct FwdParams {
     float* alpha_out;
     float* depth_out;
     const uint32_t* tilebox;
-    const uint4* pixbox;        // [bs, nf] x0 | x1 << 16, y0 | y1 << 16, bits of the face's margin (face_margin_px), -
+    const uint4* pixbox;        // [bs, nf] x0 | x1 << 16, y0 | y1 << 16, bits of the face's margin (face_margin_px), -; thin faces: the box their
+                                // rows and row intervals are clipped to (the dilated box of a bounded sliver, else the whole screen)
     const uint32_t* tile_off;   // [bs, ntiles + 1]
     const uint32_t* tile_list;  // [bs, list_cap]
     const uint32_t* overflow;   // [bs]
     const uint32_t* tile_order; // [bs * ntiles] launch rank -> b * ntiles + tile, heaviest lists first
     const uint32_t* thin_count; // [bs]
-    const float4* thin_list;    // [bs, 2, nf]: {nx, ny, a . n, band} of every thin face, then {ax, ay, face index bits, -}
+    const float4* thin_list;    // [bs, 2, nf]: {nx, ny, a . n, band} of every thin face, then {ax, ay, face index bits, tile range in tilebox's packing}
     unsigned long long* counters;  // [16] candidate pixel tests, tests passed, depth keys submitted, phase clocks (COUNT builds only)
     uint32_t list_cap;
     double eps;
@@ -135,6 +137,12 @@ constexpr int HIST_MAX = 4096;  // tiles per image that fit the LDS histogram (S
 // (k_face_normals_gather's operations).  What sdn_render_maps_fwd used to issue as k_face_normals_gather + k_project +
 // k_gather_faces + k_face_setup (61 us of a 16-object frame, the projected vertices and the face tensor written and read back)
 // is this one launch; the values are the same floats, so everything downstream is bit-identical.
+// Thin faces (<false, *>; margin not in (0, THIN_MARGIN]) get no tile box but a record in the thin list for the band path of
+// k_raster_tiles: the line through the longest edge, the band's half width, and the box no passing pixel can leave -- the dilated
+// box of a sliver with a finite margin (tile range in the record, pixel box in pixbox), the whole screen otherwise.  A thin face
+// whose box misses the screen gets no record, and neither does a face with a repeated vertex (the argument is next to the code):
+// both end here as culled faces, under GATHER with none of their per-face data stored -- they own no pixel, so neither the
+// epilogue nor the backward pass can ask for it.
 template <bool K1, bool GATHER>
 __global__ __launch_bounds__(256) void k_face_setup(const float* __restrict__ faces, int nf, int S, int ntx,
                                                      float* __restrict__ face_inv, uint32_t* __restrict__ tilebox,
@@ -288,11 +296,48 @@ __global__ __launch_bounds__(256) void k_face_setup(const float* __restrict__ fa
                 cmax = fmaxf(cmax, fmaxf(fabsf(f[6]), fabsf(f[7])));
                 const float delta_px = 9.5367432e-7f * (1.0f + cmax) * 0.5f * (float)S;
                 const float band = h + 0.05f + 2.5f * delta_px + 4e-6f * (pmax + (float)S);
-                const uint32_t slot = atomicAdd(&thin_count[b], 1u);
-                float4* e = thin_list + (size_t)b * nf * 2;      // [nf] cull records, then [nf] face records
-                e[slot] = make_float4(nx, ny, px[ia] * nx + py[ia] * ny, band);
-                e[nf + slot] = make_float4(px[ia], py[ia], __uint_as_float((uint32_t)fn_local), 0.f);
-                thin = true;
+                // (1) A face with a REPEATED VERTEX never records a pixel and is dropped here.  Two vertices whose NDC x and y
+                // agree bit for bit have bit-identical pixel coordinates, so face_inverse computes den == 0 exactly (its two
+                // non-zero products are exact negatives of each other; no contraction in this file): the inverse's row of the
+                // lone vertex is 0 / 0 = NaN, the two other rows are +-inf or NaN, each the negation of the other.  bary_weights
+                // gets t = +inf in a row (A, B, C) / 0 only if A fx, B fy and C are all non-zero and of one sign; that needs
+                // fx, fy >= 1 and puts the pixel |A fx + B fy + C| / L = (|A| fx + |B| fy + |C|) / L >= (|A| + |B|) / L >= 1
+                // pixel from the line A x + B y + C = 0 through the two distinct vertices (L = its length |(A, B)|).  But a pixel
+                // passes the edge tests only within `band` of that line (h = 0 here: 0.05 px plus the rounding terms), so
+                // wherever the tests pass all three weights clamp to 0 (fmax / fmin drop the NaN), their sum is 0, the weights
+                // 0 / 0 and the depth NaN, and `zp > near_le && zp < far_f` is false: nothing reaches the z-buffer.  The argument
+                // needs band < 1; faces whose coordinates are so large that the rounding terms approach a pixel keep the band path.
+                const bool repeated = (__float_as_uint(f[0]) == __float_as_uint(f[3]) && __float_as_uint(f[1]) == __float_as_uint(f[4])) ||
+                                      (__float_as_uint(f[0]) == __float_as_uint(f[6]) && __float_as_uint(f[1]) == __float_as_uint(f[7])) ||
+                                      (__float_as_uint(f[3]) == __float_as_uint(f[6]) && __float_as_uint(f[4]) == __float_as_uint(f[7]));
+                // (2) A sliver with a finite margin (THIN_MARGIN < m < S) can pass the edge tests only inside its dilated box, like
+                // any ordinary face: face_margin_px bounds m whatever its size, THIN_MARGIN only picks the cheaper of two exact
+                // candidate sets.  The record carries the box (tiles and pixels), clipped to the screen; a box that misses the
+                // screen or holds no pixel centre means no record at all.  m = -1 (no usable area, or m >= S): the whole screen.
+                int bx0 = 0, bx1 = S - 1, by0 = 0, by1 = S - 1;
+                bool boxed_out = false;
+                if (m > 0.0f) {
+                    const float fx0 = ceilf(xmin - m), fx1 = floorf(xmax + m);
+                    const float fy0 = ceilf(ymin - m), fy1 = floorf(ymax + m);
+                    if (fx1 < 0.0f || fy1 < 0.0f || fx0 > (float)(S - 1) || fy0 > (float)(S - 1) || fx0 > fx1 || fy0 > fy1) {
+                        boxed_out = true;
+                    } else {
+                        bx0 = (int)fmaxf(fx0, 0.0f);
+                        by0 = (int)fmaxf(fy0, 0.0f);
+                        bx1 = (int)fminf(fx1, (float)(S - 1));
+                        by1 = (int)fminf(fy1, (float)(S - 1));
+                    }
+                }
+                if (!(repeated && band < 0.5f) && !boxed_out) {
+                    const uint32_t trange = (uint32_t)(bx0 / TS) | ((uint32_t)(bx1 / TS) << 8) | ((uint32_t)(by0 / TS) << 16) |
+                                            ((uint32_t)(by1 / TS) << 24);
+                    pb = make_uint4((uint32_t)bx0 | ((uint32_t)bx1 << 16), (uint32_t)by0 | ((uint32_t)by1 << 16), __float_as_uint(m), 0u);
+                    const uint32_t slot = atomicAdd(&thin_count[b], 1u);
+                    float4* e = thin_list + (size_t)b * nf * 2;      // [nf] cull records, then [nf] face records
+                    e[slot] = make_float4(nx, ny, px[ia] * nx + py[ia] * ny, band);
+                    e[nf + slot] = make_float4(px[ia], py[ia], __uint_as_float((uint32_t)fn_local), __uint_as_float(trange));
+                    thin = true;
+                }
             }
         } else {
             // pixel centres sit at integer pixel coordinates: candidates are the integers inside the dilated box
@@ -763,6 +808,7 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
     const float4* thin_cull = P.thin_list + (size_t)b * nf * 2;   // {nx, ny, a . n, band}
     const uint32_t n_thin = P.thin_count[b];
     const float4 thin_c0 = thin_cull[min(tid, 2 * nf - 1)];
+    const uint32_t thin_r0 = reinterpret_cast<const uint32_t*>(thin_cull + nf + min(tid, nf - 1))[3];   // (its tile range)
     const uint32_t* tb = P.tilebox + (size_t)b * nf;
     const uint4* pbx = P.pixbox + (size_t)b * nf;
     const float* faces_b = P.faces + (size_t)b * nf * 9;
@@ -1037,8 +1083,16 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
     // ---- slivers / degenerate faces: band test around their line instead of a bounding box ---------------------
     // Meshes carry them (every pole triangle of a UV sphere has two coincident vertices; ~0.4 % of a CAD file's faces): such a
     // face can win pixels anywhere along the line through its longest edge.  thin_cull: the 256 threads look at different thin
-    // faces each and queue the few whose band comes near this tile; thin_items: only those are tested, pixel by pixel.
-    const float4* thin_recs = thin_cull + nf;                            // {ax, ay, face index bits, -}
+    // faces each and queue the few whose band comes near this tile AND whose box (k_face_setup: the dilated box of a sliver with a
+    // finite margin, else the whole screen) holds it; thin_items: only those are tested, pixel by pixel, inside that box.
+    // This is the only work of a tile that does not follow its list -- every tile of an object, the empty ones included, looks at
+    // all of the object's thin records.  Faces with a repeated vertex (half of a CAD file's thin faces) no longer get a record,
+    // and the box takes nine tenths of the (face, tile) pairs the line alone queued: k_raster_tiles 246 -> 225 us per launch on
+    // cad_like, 172 -> 156 on car_like (profiles/thin_band_path.md).  With that the rest of the path no longer shows in the
+    // launch time: compiled out altogether (SDN_LAB_NO_THIN, SDN_LAB_NO_THIN_CULL) the launch takes the same 222 .. 227 us, and
+    // hoisting 1 / nx out of the row loop, loading the face with its records and 2 or 4 rows per item all measured inside that
+    // range -- the loop below is left as it was.
+    const float4* thin_recs = thin_cull + nf;                            // {ax, ay, face index bits, tile range}
     auto thin_cull_pass = [&]() {   // q_count == 0 on entry; barrier needed after
         const float cx = (float)X0 + 0.5f * (float)(TS - 1), cy = (float)Y0 + 0.5f * (float)(TS - 1);
         const float reach = 0.7072f * (float)TS + 0.4f;  // half diagonal of the tile (+ 1 pixel of slack)
@@ -1046,6 +1100,9 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
         for (uint32_t t = tid; t < n_thin; t += NTHR) {
             const float4 c = t < (uint32_t)NTHR ? thin_c0 : thin_cull[t];
             if (fabsf(cx * c.x + cy * c.y - c.z) > c.w + reach) continue;  // tile too far from the face's line
+            // ... or outside the tiles of its dilated box (bounded slivers; the whole screen for the rest)
+            const uint32_t v = t < (uint32_t)NTHR ? thin_r0 : reinterpret_cast<const uint32_t*>(thin_recs + t)[3];
+            if ((uint32_t)tx < (v & 255u) || (uint32_t)tx > ((v >> 8) & 255u) || (uint32_t)ty < ((v >> 16) & 255u) || (uint32_t)ty > (v >> 24)) continue;
             const uint32_t slot = atomicAdd(&q_count, 1u);
             if (slot < (uint32_t)QCAP) q_fn[slot] = t;
         }
@@ -1073,20 +1130,26 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
             const float4 e0 = thin_cull[t], e1 = thin_recs[t];
             const float nx = e0.x, ny = e0.y, band = e0.w, ax = e1.x, ay = e1.y;
             const uint32_t qf = __float_as_uint(e1.z);
+            // the face's pixel box, clipped to the tile: nothing outside it can pass the edge tests (k_face_setup, (2)), so rows
+            // and row intervals stop at it.  (The queue-overflow walk of the whole list is culled by it as well.)
+            const uint4 pbq = pbx[qf];
+            const int cx0 = max((int)(pbq.x & 0xffffu) - X0, 0), cx1 = min((int)(pbq.x >> 16) - X0, TS - 1);
+            const int cy0 = max((int)(pbq.y & 0xffffu) - Y0, g * ROWS_PER_ITEM), cy1 = min((int)(pbq.y >> 16) - Y0, (g + 1) * ROWS_PER_ITEM - 1);
+            if (cx0 > cx1) continue;
             float f[9];
             bool loaded = false;
-            for (int py = g * ROWS_PER_ITEM; py < (g + 1) * ROWS_PER_ITEM; py++) {
+            for (int py = cy0; py <= cy1; py++) {
                 // pixels of this row with |(x - ax) nx + (y - ay) ny| <= band: an interval in x (one pixel of slack either side;
                 // the exact predicate below decides), the whole row when the line runs (nearly) along it
                 const float off = ((float)(Y0 + py) - ay) * ny;
-                int lo = 0, hi = TS - 1;
+                int lo = cx0, hi = cx1;
                 if (fabsf(nx) > 1e-3f) {
                     const float r = 1.0f / nx;
                     const float xa = ax + (-band - off) * r, xb = ax + (band - off) * r;
                     const float x_lo = fminf(xa, xb) - (float)X0 - 1.0f, x_hi = fmaxf(xa, xb) - (float)X0 + 1.0f;
                     if (!(x_lo <= (float)(TS - 1)) || !(x_hi >= 0.0f)) continue;       // (also skips NaN)
-                    lo = max(0, (int)fmaxf(x_lo, 0.0f));
-                    hi = min(TS - 1, (int)fminf(x_hi, (float)(TS - 1)));
+                    lo = max(cx0, (int)fmaxf(x_lo, 0.0f));
+                    hi = min(cx1, (int)fminf(x_hi, (float)(TS - 1)));
                 } else if (fabsf(off + ((float)X0 + 0.5f * (float)(TS - 1) - ax) * nx) > band + 0.5f * (float)TS * fabsf(nx) + 1.0f) {
                     continue;
                 }
@@ -1121,9 +1184,10 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
         const int ntiles = P.ntx * P.ntx;
         const uint32_t* off = P.tile_off + (size_t)b * (ntiles + 1);
         const uint32_t lo = off[tile], hi = off[tile + 1];
+        tick(c_fetch);   // (the tile's initialisation)
         thin_cull_pass();
         __syncthreads();
-        tick(c_fetch);
+        tick(c_thin);   // (the cull pass and its barrier belong to the band path)
         const uint32_t* lst = P.tile_list + (size_t)b * P.list_cap + lo;
         const int n_list = (int)(hi - lo);
         hiz_on = n_list >= HIZ_MIN_LIST;
