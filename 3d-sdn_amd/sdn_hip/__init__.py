@@ -126,6 +126,10 @@ def _declare(L):
     sig['sdn_inst_index_workspace_bytes'] = [ctypes.POINTER(_sz)]
     sig['sdn_inst_index_build'] = [_vp, _ci, _ci, _ci, _ci, _vp, _sz, _vp, _vp, _cl, _vp]
     sig['sdn_inst_index_rank'] = [_vp, _ci, _ci, _ci, _ci, _vp, _sz, _vp, _vp, _vp]
+    sig['sdn_mrcnn_loss_workspace_bytes'] = [_ci, _ci, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
+    _mrl_inputs = [_vp, _ci, _vp, _vp, _vp, _ci, _ci, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _ci, _ci]
+    sig['sdn_mrcnn_loss_fwd'] = _mrl_inputs + [_vp, _sz, _vp, _sz, _vp, _vp, _vp]
+    sig['sdn_mrcnn_loss_bwd'] = _mrl_inputs + [_vp, _sz, _vp] + [_vp] * 5 + [_vp]
     sig['sdn_train_losses_scratch'] = [_ci, _ci, _cl, ctypes.POINTER(_sz)]
     sig['sdn_train_losses_fwd'] = [_vp] * 7 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp]
     sig['sdn_train_losses_bwd'] = [_vp] * 6 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd] + [_vp] * 9 + [_vp]
@@ -164,7 +168,7 @@ def _declare(L):
         try:
             fn = getattr(L, name)
         except AttributeError:
-            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*): a library built before them is stale
+            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*): a library built before them is stale
             raise SdnHipError('%s does not export %s -- rebuild it (`python __graft_entry__.py build`)' % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = _ci
@@ -210,6 +214,7 @@ def exported_symbols():
             'sdn_segm_fuse', 'sdn_segm_labels_from_colors', 'sdn_segm_confusion', 'sdn_segm_train_batch', 'sdn_segm_loss_fwd', 'sdn_segm_loss_bwd',
             'sdn_segm_ppm_pool', 'sdn_segm_ppm_fill', 'sdn_segm_ppm_fill_bwd', 'sdn_segm_ppm_pool_bwd',
             'sdn_encode_maps', 'sdn_inst_index_workspace_bytes', 'sdn_inst_index_build', 'sdn_inst_index_rank',
+            'sdn_mrcnn_loss_workspace_bytes', 'sdn_mrcnn_loss_fwd', 'sdn_mrcnn_loss_bwd',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',

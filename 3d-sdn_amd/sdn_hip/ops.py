@@ -1607,6 +1607,125 @@ def segm_loss(scores, scores_deepsup, seg_label, deep_sup_scale):
     return SegmLossFn.apply(scores, scores_deepsup, seg_label, 0.0 if deep_sup_scale is None else deep_sup_scale)
 
 
+MRCNN_LOSS_CHUNK, MRCNN_MAX_CLASSES, MRCNN_MAX_ANCHORS = 1024, 128, 1 << 24   # csrc/mrcnn_loss_check.h: MRL_CHUNK, MRL_MAX_CLASSES, MRL_MAX_ANCHORS
+_MRCNN_INTS = (torch.int32, torch.int64)
+
+
+def mrcnn_loss_bytes(A, R):
+    """(bytes of `workspace`, bytes of `saved`) of sdn_mrcnn_loss_fwd / _bwd, asked of the library"""
+    wb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(lib().sdn_mrcnn_loss_workspace_bytes(int(A), int(R), ctypes.byref(wb), ctypes.byref(sb)))
+    return wb.value, sb.value
+
+
+class MrcnnLossFn(torch.autograd.Function):
+    """compute_losses of the reference's Mask R-CNN (geometric/maskrcnn/model.py:1004-1147) and the sum of :1955 --
+    sdn_mrcnn_loss_fwd / _bwd (include/sdn_hip.h), forward in three launches, backward in one.  Returns (out fp32 [6]: the five
+    losses and their sum; counts int64 [4]: n_rpn_valid, n_rpn_pos, n_roi_pos, bad).  The five head arguments are None for R = 0.
+    `mrcnn_loss` below checks types and shapes; a CPU tensor raises NotImplementedError here."""
+
+    @staticmethod
+    def forward(ctx, rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_class_ids, mrcnn_class_logits, target_deltas,
+                mrcnn_bbox, target_mask, mrcnn_mask):
+        match = want(rpn_match, rpn_match.dtype, 'rpn_match')
+        tb, xl, xb = _f32(rpn_bbox, 'rpn_bbox'), _f32(rpn_class_logits, 'rpn_class_logits'), _f32(rpn_pred_bbox, 'rpn_pred_bbox')
+        ids = want(target_class_ids, target_class_ids.dtype, 'target_class_ids') if target_class_ids is not None else None
+        hl, hd, hb = _f32(mrcnn_class_logits, 'mrcnn_class_logits'), _f32(target_deltas, 'target_deltas'), _f32(mrcnn_bbox, 'mrcnn_bbox')
+        tm, hm = _f32(target_mask, 'target_mask'), _f32(mrcnn_mask, 'mrcnn_mask')
+        batch, A, T = xl.shape[0], xl.shape[1], tb.shape[1]
+        R, (C, h, w) = (0, (0, 0, 0)) if ids is None else (hm.shape[0], hm.shape[1:])
+        sizes = (batch, A, T, R, C, h, w)
+        flags = (int(match.dtype == torch.int64), int(ids is not None and ids.dtype == torch.int64))
+        dev = xl.device
+        with torch.cuda.device(dev):
+            wbytes, sbytes = mrcnn_loss_bytes(A, R)
+            work = torch.empty(wbytes, dtype=torch.uint8, device=dev)
+            saved = torch.empty(sbytes, dtype=torch.uint8, device=dev)
+            out = torch.empty(6, dtype=torch.float32, device=dev)
+            counts = torch.empty(4, dtype=torch.int64, device=dev)
+            check(lib().sdn_mrcnn_loss_fwd(ptr(match), flags[0], ptr(tb), ptr(xl), ptr(xb), batch, A, T, ptr(ids), flags[1], ptr(hl), ptr(hd),
+                                           ptr(hb), ptr(tm), ptr(hm), R, C, h, w, ptr(work), wbytes, ptr(saved), sbytes, ptr(out),
+                                           ptr(counts), stream()))
+        ctx.save_for_backward(match, tb, xl, xb, ids, hl, hd, hb, tm, hm, saved)
+        ctx.sizes, ctx.flags = sizes, flags
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out, _g_counts):
+        match, tb, xl, xb, ids, hl, hd, hb, tm, hm, saved = ctx.saved_tensors
+        batch, A, T, R, C, h, w = ctx.sizes
+        need = [ctx.needs_input_grad[i] and t is not None for i, t in ((2, xl), (3, xb), (5, hl), (7, hb), (9, hm))]
+        grads = [None] * 10
+        if not any(need):
+            return tuple(grads)
+        with torch.cuda.device(xl.device):
+            go = g_out.to(torch.float32).contiguous()
+            gs = [torch.empty_like(t) if n else None for n, t in zip(need, (xl, xb, hl, hb, hm))]
+            check(lib().sdn_mrcnn_loss_bwd(ptr(match), ctx.flags[0], ptr(tb), ptr(xl), ptr(xb), batch, A, T, ptr(ids), ctx.flags[1], ptr(hl),
+                                           ptr(hd), ptr(hb), ptr(tm), ptr(hm), R, C, h, w, ptr(saved), saved.numel(), ptr(go), ptr(gs[0]),
+                                           ptr(gs[1]), ptr(gs[2]), ptr(gs[3]), ptr(gs[4]), stream()))
+        for i, g in zip((2, 3, 5, 7, 9), gs):
+            grads[i] = g
+        return tuple(grads)
+
+
+def mrcnn_loss(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_class_ids, mrcnn_class_logits, target_deltas, mrcnn_bbox,
+               target_mask, mrcnn_mask):
+    """(out fp32 [6] = rpn_class_loss, rpn_bbox_loss, mrcnn_class_loss, mrcnn_bbox_loss, mrcnn_mask_loss and their sum; counts
+    int64 [4] = n_rpn_valid, n_rpn_pos, n_roi_pos, bad) of a Mask R-CNN training step, the arguments of the reference's
+    compute_losses (model.py:1139): rpn_match int32 / int64 [1, A, 1], rpn_bbox fp32 [1, T, 4], rpn_class_logits fp32 [1, A, 2],
+    rpn_pred_bbox fp32 [1, A, 4], target_class_ids int32 / int64 [R], mrcnn_class_logits fp32 [R, C], target_deltas fp32 [R, 4],
+    mrcnn_bbox fp32 [R, C, 4], target_mask fp32 [R, h, w], mrcnn_mask fp32 [R, C, h, w].  An empty target_class_ids means R = 0: the
+    other head tensors are not looked at.  Differentiable in the five predictions; the targets get no gradient and counts is not
+    differentiable.  Nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape ValueError, a CPU tensor
+    NotImplementedError."""
+    named = (('rpn_match', rpn_match, _MRCNN_INTS), ('rpn_bbox', rpn_bbox, (torch.float32,)),
+             ('rpn_class_logits', rpn_class_logits, (torch.float32,)), ('rpn_pred_bbox', rpn_pred_bbox, (torch.float32,)),
+             ('target_class_ids', target_class_ids, _MRCNN_INTS), ('mrcnn_class_logits', mrcnn_class_logits, (torch.float32,)),
+             ('target_deltas', target_deltas, (torch.float32,)), ('mrcnn_bbox', mrcnn_bbox, (torch.float32,)),
+             ('target_mask', target_mask, (torch.float32,)), ('mrcnn_mask', mrcnn_mask, (torch.float32,)))
+    for name, t, _ in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    R = target_class_ids.numel()
+    for name, t, dtypes in (named if R else named[:4]):
+        if t.dtype not in dtypes:
+            raise TypeError('%s must be %s, got %s' % (name, ' or '.join(str(d) for d in dtypes), t.dtype))
+        if t.device != rpn_class_logits.device:
+            raise ValueError('%s is on %s, rpn_class_logits on %s' % (name, t.device, rpn_class_logits.device))
+    if rpn_class_logits.dim() != 3 or rpn_class_logits.shape[2] != 2 or rpn_class_logits.shape[1] < 1:
+        raise ValueError('rpn_class_logits must be fp32 [1, A, 2], got %s' % (tuple(rpn_class_logits.shape),))
+    batch, A = rpn_class_logits.shape[:2]
+    if batch != 1:
+        raise ValueError('the RPN tensors have batch %d; only one image per step is supported: the reference trims the targets with '
+                         'target_bbox[0, :n] (geometric/maskrcnn/model.py:1053), which has no meaning for more' % batch)
+    if A > MRCNN_MAX_ANCHORS:
+        raise ValueError('%d anchors; at most %d are supported' % (A, MRCNN_MAX_ANCHORS))
+    if tuple(rpn_match.shape) != (1, A, 1):
+        raise ValueError('rpn_match must be [1, %d, 1], got %s' % (A, tuple(rpn_match.shape)))
+    if tuple(rpn_pred_bbox.shape) != (1, A, 4):
+        raise ValueError('rpn_pred_bbox must be fp32 [1, %d, 4], got %s' % (A, tuple(rpn_pred_bbox.shape)))
+    if rpn_bbox.dim() != 3 or rpn_bbox.shape[0] != 1 or rpn_bbox.shape[1] < 1 or rpn_bbox.shape[2] != 4:
+        raise ValueError('rpn_bbox must be fp32 [1, T, 4], got %s' % (tuple(rpn_bbox.shape),))
+    if R == 0:
+        return MrcnnLossFn.apply(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, None, None, None, None, None, None)
+    if target_class_ids.dim() != 1:
+        raise ValueError('target_class_ids must be [R], got %s' % (tuple(target_class_ids.shape),))
+    if mrcnn_mask.dim() != 4 or mrcnn_mask.shape[0] != R or min(mrcnn_mask.shape) < 1:
+        raise ValueError('mrcnn_mask must be fp32 [%d, C, h, w], got %s' % (R, tuple(mrcnn_mask.shape)))
+    _, C, h, w = mrcnn_mask.shape
+    if C < 2 or C > MRCNN_MAX_CLASSES:
+        raise ValueError('mrcnn_mask is %s; 2 to %d classes are supported' % (tuple(mrcnn_mask.shape), MRCNN_MAX_CLASSES))
+    for name, t, shape in (('mrcnn_class_logits', mrcnn_class_logits, (R, C)), ('target_deltas', target_deltas, (R, 4)),
+                           ('mrcnn_bbox', mrcnn_bbox, (R, C, 4)), ('target_mask', target_mask, (R, h, w))):
+        if tuple(t.shape) != shape:
+            raise ValueError('%s must be fp32 %s, got %s' % (name, list(shape), tuple(t.shape)))
+    return MrcnnLossFn.apply(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_class_ids, mrcnn_class_logits, target_deltas,
+                             mrcnn_bbox, target_mask, mrcnn_mask)
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

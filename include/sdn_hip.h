@@ -75,7 +75,8 @@ const char* sdn_last_error(void);
  * added; 17: sdn_train_id_stats_workspace_bytes, sdn_train_id_stats, sdn_train_crops_mixed added; 18: sdn_segm_fuse,
  * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added; 20: sdn_segm_loss_fwd,
  * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added; still 20: sdn_encode_maps,
- * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added -- new entry
+ * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added; still 20: sdn_mrcnn_loss_workspace_bytes,
+ * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -932,6 +933,52 @@ int sdn_inst_index_build(void* inst, int inst_dtype, int N, int H, int W, void* 
                          int64_t* counts, long id_capacity, sdnStream stream);
 int sdn_inst_index_rank(const void* inst, int inst_dtype, int N, int H, int W, const void* workspace, size_t workspace_bytes,
                         int32_t* seg, int64_t* counts, sdnStream stream);
+
+/* ---- the training losses of Mask R-CNN: geometric/maskrcnn/model.py:1004-1147 (compute_losses and the five functions it calls)
+ * and the sum of :1955 (csrc/mrcnn_loss.hip) --------------------------------------------------------------------------------------------
+ * The reference selects the contributing anchors and RoIs with four torch.nonzero calls (:1020, 1047, 1091, 1121; each one waits
+ * for the device), gathers through index tensors, runs cross_entropy twice, smooth_l1_loss twice and binary_cross_entropy once, and
+ * backward turns every gather into a zero fill and an index_put.  Everything below is DEVICE memory, contiguous.
+ *   rpn_match [1, A, 1] int32 (match_i64 = 0) or int64 (1): 1 positive, -1 negative, 0 neutral; rpn_bbox fp32 [1, T, 4] (targets);
+ *   rpn_class_logits fp32 [1, A, 2]; rpn_pred_bbox fp32 [1, A, 4]; `batch` is their first dimension and must be 1 (:1053).
+ *   target_class_ids [R] int32 (ids_i64 = 0) or int64 (1); mrcnn_class_logits fp32 [R, C]; target_deltas fp32 [R, 4]; mrcnn_bbox
+ *   fp32 [R, C, 4]; target_mask fp32 [R, h, w]; mrcnn_mask fp32 [R, C, h, w], probabilities.  With R = 0 the head tensors are not
+ *   read (they may be NULL) and the three head losses are 0 (:1070, 1088, 1118).
+ * 1 <= A <= 2^24, 1 <= T, 0 <= R, 2 <= C <= 128, R * C * h * w < 2^31.
+ *
+ * sdn_mrcnn_loss_workspace_bytes: the sizes of `workspace` (forward only; nothing needs zeroing) and `saved` (written by forward,
+ *   read by backward: the four selection counts, the RoIs' log-sum-exps, the positive anchors before every chunk of 1024 anchors).
+ * sdn_mrcnn_loss_fwd, three launches (replaces :1004-1147 and :1955):
+ *   out fp32 [6]: rpn_class_loss (:1004-1029: mean over the anchors with match != 0 of the 2-class cross entropy against
+ *     [match == 1]), rpn_bbox_loss (:1032-1058: the k-th positive anchor in anchor order against target row k, smooth L1 with beta
+ *     1, mean over 4 n_rpn_pos), mrcnn_class_loss (:1061-1077: mean cross entropy over the RoIs), mrcnn_bbox_loss (:1080-1106:
+ *     smooth L1 over the RoIs with id > 0, the deltas of the RoI's class, mean over 4 n_roi_pos), mrcnn_mask_loss (:1109-1136:
+ *     torch's binary_cross_entropy, each log clamped at -100, of the positive RoIs' class plane, mean over n_roi_pos h w), and
+ *     their sum (:1955).  Each element is evaluated in fp64, each loss summed in fp64 in a fixed order and rounded to fp32 once;
+ *     the sum is the fp64 sum of the five, rounded once.  A mean over an empty selection is NaN, as torch's.
+ *   counts int64 [4]: n_rpn_valid (match 1 or -1), n_rpn_pos (the positives in the box loss), n_roi_pos, bad.  `bad` counts what
+ *     the reference has no defined answer for, each left out of its loss: an rpn_match value outside {-1, 0, 1}; a positive anchor
+ *     with T or more positives before it (it stays in the class loss); a target_class_ids value outside [0, C) (the RoI is left
+ *     out of all three head losses and of their divisors).  A mask probability outside [0, 1] makes that loss NaN.
+ * sdn_mrcnn_loss_bwd, one launch (the autograd of the above): grad_out fp32 [6], the gradient of `out`; each of the five gradients
+ *   has the shape of its input and may be NULL (skipped; not all).  Every element of a given one is written exactly once, +0.0
+ *   outside the selections; the binary cross entropy's is torch's (p - y) / max((1 - p) p, 1e-12).  The targets get none.
+ * SDN_EINVAL with a message before any launch for a NULL or misaligned pointer, a batch other than 1 and sizes outside the above.
+ * A lane takes four adjacent anchors: 16-byte loads and stores of rpn_match, the logits and the [A, 4] rows when all RPN bases are
+ * 16-byte aligned, and of the mask planes when h * w % 4 == 0 and their bases are; scalar ones otherwise.  No atomics, no
+ * workgroup waits for another; identical from run to run; nothing crosses to the host. */
+int sdn_mrcnn_loss_workspace_bytes(int A, int R, size_t* workspace_bytes, size_t* saved_bytes);
+int sdn_mrcnn_loss_fwd(const void* rpn_match, int match_i64, const float* rpn_bbox, const float* rpn_class_logits,
+                       const float* rpn_pred_bbox, int batch, int A, int T, const void* target_class_ids, int ids_i64,
+                       const float* mrcnn_class_logits, const float* target_deltas, const float* mrcnn_bbox, const float* target_mask,
+                       const float* mrcnn_mask, int R, int C, int h, int w, void* workspace, size_t workspace_bytes, void* saved,
+                       size_t saved_bytes, float* out, int64_t* counts, sdnStream stream);
+int sdn_mrcnn_loss_bwd(const void* rpn_match, int match_i64, const float* rpn_bbox, const float* rpn_class_logits,
+                       const float* rpn_pred_bbox, int batch, int A, int T, const void* target_class_ids, int ids_i64,
+                       const float* mrcnn_class_logits, const float* target_deltas, const float* mrcnn_bbox, const float* target_mask,
+                       const float* mrcnn_mask, int R, int C, int h, int w, const void* saved, size_t saved_bytes, const float* grad_out,
+                       float* grad_rpn_class_logits, float* grad_rpn_pred_bbox, float* grad_mrcnn_class_logits, float* grad_mrcnn_bbox,
+                       float* grad_mrcnn_mask, sdnStream stream);
 
 /* ---- the 2D and 2D+ edit baselines: geometric/scripts/main.py:215-322 (_test_2d, _test_2d_plus), the loop at :293-312 ----------
  * The reference, per object and frame: slices the detector mask at its roi, fetches it to the host, PIL-resizes it (bilinear)
