@@ -1,0 +1,225 @@
+// Mask R-CNN's pyramid RoIAlign for gfx950: every box sampled from the FPN level its area selects, one launch forward, a zero fill
+// and one scatter launch backward.
+//
+// Reference: geometric/maskrcnn/model.py:414-502 (pyramid_roi_align) with log2 of :95-100, and the crop it calls per level,
+// roialign/roi_align/src/crop_and_resize.c:7-251.  The reference finds each level's boxes on the host (ix.any(), torch.nonzero: two
+// waits per level), crops level by level, concatenates, sorts and gathers the result back into box order.  None of that needs the
+// host: a box's level is a function of its four numbers, and the output row of box r is row r.
+//
+//   k_pra_fwd   a workgroup owns one box and a chunk of PRA_CHANNELS channels.  It computes the box's level (fp32, operation for
+//               operation as model.py:445-457; no fast-math intrinsics) and builds the pool x pool sample table ONCE in LDS: four tap
+//               offsets inside a channel plane, the two lerp weights and an inside flag per sample -- the arithmetic of k_crop_fwd
+//               (crop_sample.h), so the values are the bits of crop_and_resize.c.  The lanes then run over (channel, sample), sample
+//               fastest: the box's C * pool^2 outputs are contiguous, so the stores are coalesced, and the taps of one box fall into
+//               a window of a few dozen pixels per channel.
+//   k_pra_zero  16-byte stores over the one allocation that holds the four maps' gradients.
+//   k_pra_bwd   the same table; fp32 atomic adds into the box's level, as k_crop_bwd and the reference's CUDA kernel.  Levels without
+//               a box stay all zero.  The order of the adds is not fixed, so the gradients are not bit-reproducible from run to run.
+//
+// A non-finite level value (a box of area <= 0, NaN) gives level 2: pyramid_roi_align_check.h, pra_level_of.
+#include "crop_sample.h"
+#include "pyramid_roi_align_check.h"
+#include "sdn_common.h"
+
+namespace sdn {
+
+struct PraParams {
+    const float* boxes;          // [R, 4] (y1, x1, y2, x2), normalised
+    const float* map[PRA_LEVELS];   // forward: [C, H_l, W_l]
+    float* gmap[PRA_LEVELS];     // backward: the level's range of the gradient buffer
+    int H[PRA_LEVELS], W[PRA_LEVELS];
+    int C, pool, chunks;
+    float image_area, extrapolation;
+    float* pooled;               // forward: [R, C, pool, pool]
+    int32_t* levels;             // forward: [R]
+    const float* grads;          // backward: [R, C, pool, pool]
+};
+
+struct PraTable {
+    int4* taps;     // top-left, top-right, bottom-left, bottom-right: offsets inside a channel plane
+    float2* lerp;   // x_lerp, y_lerp
+    int* inside;
+};
+
+// the dynamic LDS, carved with the 16-byte entries first; nothing static lies in front of it
+__device__ __forceinline__ PraTable pra_table(unsigned char* lds, int pp)
+{
+    PraTable t;
+    t.taps = reinterpret_cast<int4*>(lds);
+    t.lerp = reinterpret_cast<float2*>(lds + (size_t)pp * 16);
+    t.inside = reinterpret_cast<int*>(lds + (size_t)pp * 24);
+    return t;
+}
+
+// The box's level index (0 = P2 .. 3 = P5), the same in every lane and returned as a scalar, and its sample table.  Ends with a barrier.
+__device__ __forceinline__ int pra_prepare(const PraParams& P, int r, const PraTable& t)
+{
+    const float* box = P.boxes + 4 * (size_t)r;
+    const float y1 = box[0], x1 = box[1], y2 = box[2], x2 = box[3];
+    const int l = __builtin_amdgcn_readfirstlane(pra_level_of(pra_level_value(y1, x1, y2, x2, P.image_area)) - 2);
+    const int H = l == 0 ? P.H[0] : l == 1 ? P.H[1] : l == 2 ? P.H[2] : P.H[3];
+    const int W = l == 0 ? P.W[0] : l == 1 ? P.W[1] : l == 2 ? P.W[2] : P.W[3];
+    const int pp = P.pool * P.pool;
+    for (int s = threadIdx.x; s < pp; s += PRA_THREADS) {
+        const int y = s / P.pool, x = s - y * P.pool;
+        const float in_y = axis_in(y1, y2, H, P.pool, y);
+        const float in_x = axis_in(x1, x2, W, P.pool, x);
+        int4 taps = make_int4(0, 0, 0, 0);
+        float2 lerp = make_float2(0.0f, 0.0f);
+        const bool inside = axis_inside(in_y, H) && axis_inside(in_x, W);
+        if (inside) {   // 0 <= in <= extent - 1, so floor and ceil are rows and columns of the map
+            const int top = (int)floorf(in_y), bottom = (int)ceilf(in_y);
+            const int left = (int)floorf(in_x), right = (int)ceilf(in_x);
+            taps = make_int4(top * W + left, top * W + right, bottom * W + left, bottom * W + right);
+            lerp = make_float2(in_x - (float)left, in_y - (float)top);
+        }
+        t.taps[s] = taps;
+        t.lerp[s] = lerp;
+        t.inside[s] = inside ? 1 : 0;
+    }
+    __syncthreads();
+    return l;
+}
+
+__global__ __launch_bounds__(PRA_THREADS) void k_pra_fwd(const PraParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char pra_lds[];
+    const int pp = P.pool * P.pool;
+    const PraTable t = pra_table(pra_lds, pp);
+    const int r = blockIdx.x / P.chunks, chunk = blockIdx.x - r * P.chunks;
+    const int l = pra_prepare(P, r, t);
+    if (chunk == 0 && threadIdx.x == 0) P.levels[r] = l + 2;
+    const float* map = l == 0 ? P.map[0] : l == 1 ? P.map[1] : l == 2 ? P.map[2] : P.map[3];
+    const int HW = l == 0 ? P.H[0] * P.W[0] : l == 1 ? P.H[1] * P.W[1] : l == 2 ? P.H[2] * P.W[2] : P.H[3] * P.W[3];
+    const int c0 = chunk * PRA_CHANNELS, nc = min(PRA_CHANNELS, P.C - c0);
+    float* out = P.pooled + ((size_t)r * P.C + c0) * pp;
+    const int total = nc * pp;
+    // element i = c * pp + s of the chunk; c and s advance without a division
+    const int dc = PRA_THREADS / pp, ds = PRA_THREADS - dc * pp;
+    int c = threadIdx.x / pp, s = threadIdx.x - c * pp;
+    for (int i = threadIdx.x; i < total; i += PRA_THREADS) {
+        float v = P.extrapolation;
+        if (t.inside[s]) {
+            const int4 o = t.taps[s];
+            const float2 w = t.lerp[s];
+            const float* p = map + (size_t)(c0 + c) * HW;
+            const float tl = p[o.x], tr = p[o.y], bl = p[o.z], br = p[o.w];
+            const float top = tl + (tr - tl) * w.x;
+            const float bottom = bl + (br - bl) * w.x;
+            v = top + (bottom - top) * w.y;
+        }
+        out[i] = v;
+        c += dc;
+        s += ds;
+        if (s >= pp) {
+            s -= pp;
+            c++;
+        }
+    }
+}
+
+__global__ __launch_bounds__(PRA_THREADS) void k_pra_zero(float4* __restrict__ p, size_t n4)
+{
+    const size_t stride = (size_t)gridDim.x * PRA_THREADS;
+    for (size_t i = (size_t)blockIdx.x * PRA_THREADS + threadIdx.x; i < n4; i += stride) p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(PRA_THREADS) void k_pra_bwd(const PraParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char pra_lds[];
+    const int pp = P.pool * P.pool;
+    const PraTable t = pra_table(pra_lds, pp);
+    const int r = blockIdx.x / P.chunks, chunk = blockIdx.x - r * P.chunks;
+    const int l = pra_prepare(P, r, t);
+    float* gmap = l == 0 ? P.gmap[0] : l == 1 ? P.gmap[1] : l == 2 ? P.gmap[2] : P.gmap[3];
+    const int HW = l == 0 ? P.H[0] * P.W[0] : l == 1 ? P.H[1] * P.W[1] : l == 2 ? P.H[2] * P.W[2] : P.H[3] * P.W[3];
+    const int c0 = chunk * PRA_CHANNELS, nc = min(PRA_CHANNELS, P.C - c0);
+    const float* g_in = P.grads + ((size_t)r * P.C + c0) * pp;
+    const int total = nc * pp;
+    const int dc = PRA_THREADS / pp, ds = PRA_THREADS - dc * pp;
+    int c = threadIdx.x / pp, s = threadIdx.x - c * pp;
+    for (int i = threadIdx.x; i < total; i += PRA_THREADS) {
+        if (t.inside[s]) {   // crop_and_resize.c:241-247
+            const int4 o = t.taps[s];
+            const float2 w = t.lerp[s];
+            float* p = gmap + (size_t)(c0 + c) * HW;
+            const float g = g_in[i];
+            const float dtop = (1.0f - w.y) * g;
+            unsafeAtomicAdd(p + o.x, (1.0f - w.x) * dtop);
+            unsafeAtomicAdd(p + o.y, w.x * dtop);
+            const float dbottom = w.y * g;
+            unsafeAtomicAdd(p + o.z, (1.0f - w.x) * dbottom);
+            unsafeAtomicAdd(p + o.w, w.x * dbottom);
+        }
+        c += dc;
+        s += ds;
+        if (s >= pp) {
+            s -= pp;
+            c++;
+        }
+    }
+}
+
+static PraParams pra_params(const float* boxes, const int* H, const int* W, int C, int pool, float image_area)
+{
+    PraParams P = {};
+    P.boxes = boxes;
+    for (int l = 0; l < PRA_LEVELS; l++) {
+        P.H[l] = H[l];
+        P.W[l] = W[l];
+    }
+    P.C = C;
+    P.pool = pool;
+    P.chunks = pra_chunks(C);
+    P.image_area = image_area;
+    return P;
+}
+
+}  // namespace sdn
+
+using namespace sdn;
+
+SDN_API int sdn_pyramid_roi_align_grad_floats(int C, const int* H, const int* W, size_t* offsets, size_t* total)
+{
+    char why[256];
+    if (pra_grad_layout(C, H, W, offsets, total, why, sizeof(why))) return fail(SDN_EINVAL, "sdn_pyramid_roi_align_grad_floats: %s", why);
+    return SDN_OK;
+}
+
+SDN_API int sdn_pyramid_roi_align_fwd(const float* boxes, int R, const float* const* maps, const int* H, const int* W, int C, int pool,
+                                      float image_area, float extrapolation, float* pooled, int32_t* levels, sdnStream stream)
+{
+    char why[256];
+    if (pra_validate_fwd(boxes, reinterpret_cast<const void* const*>(maps), H, W, R, C, pool, image_area, pooled, levels, why, sizeof(why)))
+        return fail(SDN_EINVAL, "sdn_pyramid_roi_align_fwd: %s", why);
+    if (R == 0) return SDN_OK;
+    PraParams P = pra_params(boxes, H, W, C, pool, image_area);
+    for (int l = 0; l < PRA_LEVELS; l++) P.map[l] = maps[l];
+    P.extrapolation = extrapolation;
+    P.pooled = pooled;
+    P.levels = levels;
+    hipLaunchKernelGGL(k_pra_fwd, dim3((unsigned)R * (unsigned)P.chunks), dim3(PRA_THREADS), pra_table_bytes(pool), (hipStream_t)stream, P);
+    return check_launch("k_pra_fwd");
+}
+
+SDN_API int sdn_pyramid_roi_align_bwd(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
+                                      float image_area, float* grad_maps, sdnStream stream)
+{
+    char why[256];
+    if (pra_validate_bwd(grads, boxes, H, W, R, C, pool, image_area, grad_maps, why, sizeof(why)))
+        return fail(SDN_EINVAL, "sdn_pyramid_roi_align_bwd: %s", why);
+    size_t offsets[PRA_LEVELS], total = 0;
+    if (pra_grad_layout(C, H, W, offsets, &total, why, sizeof(why))) return fail(SDN_EINVAL, "sdn_pyramid_roi_align_bwd: %s", why);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t n4 = total / PRA_ALIGN_FLOATS;   // every range is a whole number of 16-byte pieces
+    const size_t want = (n4 + PRA_THREADS * 4 - 1) / (PRA_THREADS * 4);   // four stores per lane
+    const unsigned blocks = (unsigned)(want < 1 ? 1 : want > 4096 ? 4096 : want);
+    hipLaunchKernelGGL(k_pra_zero, dim3(blocks), dim3(PRA_THREADS), 0, st, reinterpret_cast<float4*>(grad_maps), n4);
+    if (int rc = check_launch("k_pra_zero")) return rc;
+    if (R == 0) return SDN_OK;
+    PraParams P = pra_params(boxes, H, W, C, pool, image_area);
+    for (int l = 0; l < PRA_LEVELS; l++) P.gmap[l] = grad_maps + offsets[l];
+    P.grads = grads;
+    hipLaunchKernelGGL(k_pra_bwd, dim3((unsigned)R * (unsigned)P.chunks), dim3(PRA_THREADS), pra_table_bytes(pool), st, P);
+    return check_launch("k_pra_bwd");
+}

@@ -14,6 +14,7 @@
 //               of every kept box (lanes = words).  The reference copies the mask to the host for this loop
 //               (nms_cuda.c:33-58); here it stays on the device, so nms() has no host round trip.
 //   k_crop_fwd / k_crop_bwd  one thread per crop element; bilinear taps exactly as CropAndResizePerBox.
+#include "crop_sample.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -99,15 +100,7 @@ struct CropParams {
     float extrapolation;
 };
 
-// crop_and_resize.c:43-58: source coordinate of output index k along one axis (float / double mixing as written there)
-__device__ __forceinline__ float axis_in(float a1, float a2, int extent, int crop, int k)
-{
-    if (crop > 1) {
-        const float scale = (a2 - a1) * (float)(extent - 1) / (float)(crop - 1);
-        return a1 * (float)(extent - 1) + (float)k * scale;
-    }
-    return (float)(0.5 * (double)(a1 + a2) * (double)(extent - 1));
-}
+// axis_in (crop_and_resize.c:43-58) lives in crop_sample.h, shared with pyramid_roi_align.hip
 
 __global__ __launch_bounds__(256) void k_crop_fwd(const CropParams P)
 {

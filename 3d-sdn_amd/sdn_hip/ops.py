@@ -1726,6 +1726,92 @@ def mrcnn_loss(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_clas
                              mrcnn_bbox, target_mask, mrcnn_mask)
 
 
+PYRAMID_LEVELS, PYRAMID_MAX_POOL, PYRAMID_CHANNELS = 4, 32, 64   # csrc/pyramid_roi_align_check.h: PRA_LEVELS, PRA_MAX_POOL, PRA_CHANNELS
+
+
+def _pra_ints(values):
+    return (ctypes.c_int * PYRAMID_LEVELS)(*[int(v) for v in values])
+
+
+def pyramid_grad_floats(C, H, W):
+    """(float offsets of the four maps' gradients, floats of the one buffer that holds them) of sdn_pyramid_roi_align_bwd, asked of
+    the library"""
+    offsets, total = (ctypes.c_size_t * PYRAMID_LEVELS)(), ctypes.c_size_t(0)
+    check(lib().sdn_pyramid_roi_align_grad_floats(int(C), _pra_ints(H), _pra_ints(W), offsets, ctypes.byref(total)))
+    return list(offsets), total.value
+
+
+class PyramidRoiAlignFn(torch.autograd.Function):
+    """pyramid_roi_align of the reference's Mask R-CNN (geometric/maskrcnn/model.py:414-502) -- sdn_pyramid_roi_align_fwd / _bwd
+    (include/sdn_hip.h), forward in one launch, backward in a zero fill and one scatter launch.  Returns (pooled fp32 [R, C, pool,
+    pool] in box order, levels int32 [R]).  `pyramid_roi_align` below checks types and shapes."""
+
+    @staticmethod
+    def forward(ctx, boxes, p2, p3, p4, p5, pool, image_area):
+        maps = (p2, p3, p4, p5)
+        R, C = boxes.shape[0], p2.shape[0]
+        H, W = [m.shape[1] for m in maps], [m.shape[2] for m in maps]
+        dev = boxes.device
+        with torch.cuda.device(dev):
+            pooled = torch.empty(R, C, pool, pool, dtype=torch.float32, device=dev)
+            levels = torch.empty(R, dtype=torch.int32, device=dev)
+            ptrs = (ctypes.c_void_p * PYRAMID_LEVELS)(*[ptr(m) for m in maps])
+            check(lib().sdn_pyramid_roi_align_fwd(ptr(boxes), R, ptrs, _pra_ints(H), _pra_ints(W), C, pool, image_area, 0.0, ptr(pooled),
+                                                  ptr(levels), stream()))
+        ctx.save_for_backward(boxes)
+        ctx.sizes = (R, C, H, W, pool, image_area)
+        ctx.mark_non_differentiable(levels)
+        return pooled, levels
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pooled, _g_levels):
+        (boxes,) = ctx.saved_tensors
+        R, C, H, W, pool, image_area = ctx.sizes
+        if not any(ctx.needs_input_grad[1:5]):
+            return (None,) * 7
+        with torch.cuda.device(boxes.device):
+            g = g_pooled.to(torch.float32).contiguous()
+            offsets, total = pyramid_grad_floats(C, H, W)
+            buf = torch.empty(total, dtype=torch.float32, device=boxes.device)
+            check(lib().sdn_pyramid_roi_align_bwd(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf), stream()))
+        views = [buf[o:o + C * h * w].view(C, h, w) if need else None for o, h, w, need in zip(offsets, H, W, ctx.needs_input_grad[1:5])]
+        return (None,) + tuple(views) + (None, None)
+
+
+def pyramid_roi_align(boxes, maps, pool, image_area):
+    """(pooled fp32 [R, C, pool, pool], levels int32 [R]) of the reference's pyramid_roi_align (model.py:414-502): boxes fp32 [R, 4] =
+    (y1, x1, y2, x2) normalised, maps = (P2, P3, P4, P5), each fp32 [C, H_l, W_l], image_area = float(image_shape[0] * image_shape[1]).
+    Row r of pooled is box r, sampled with crop_and_resize's arithmetic from level levels[r] (2 .. 5; a box of area <= 0 or with a NaN
+    goes to level 2).  Differentiable in the four maps only: the boxes get None (the reference detaches them, :473), levels is not
+    differentiable.  The four gradients are views of one buffer; they are sums of fp32 atomic adds and so not bit-reproducible from
+    run to run.  Nothing is copied to the host in either direction.  A wrong type or dtype raises TypeError, a wrong shape or a
+    non-contiguous tensor ValueError, a CPU tensor NotImplementedError."""
+    maps = tuple(maps)
+    if len(maps) != PYRAMID_LEVELS:
+        raise ValueError('%d feature maps; the four levels P2 .. P5 are needed' % len(maps))
+    named = [('boxes', boxes)] + [('P%d' % (l + 2), m) for l, m in enumerate(maps)]
+    for name, t in named:
+        if want(t, torch.float32, name) is not t:       # TypeError / NotImplementedError; a copy means it was not contiguous
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+        if t.device != boxes.device:
+            raise ValueError('%s is on %s, boxes on %s' % (name, t.device, boxes.device))
+    if boxes.dim() != 2 or boxes.shape[1] != 4:
+        raise ValueError('boxes must be fp32 [R, 4], got %s' % (tuple(boxes.shape),))
+    for name, m in named[1:]:
+        if m.dim() != 3 or min(m.shape) < 1:
+            raise ValueError('%s must be fp32 [C, H, W] with no empty axis, got %s' % (name, tuple(m.shape)))
+        if m.shape[0] != maps[0].shape[0]:
+            raise ValueError('%s has %d channels, P2 %d' % (name, m.shape[0], maps[0].shape[0]))
+    pool = int(pool)
+    if pool < 1 or pool > PYRAMID_MAX_POOL:
+        raise ValueError('pool %d; 1 to %d are supported' % (pool, PYRAMID_MAX_POOL))
+    image_area = float(image_area)
+    if not (0.0 < image_area < float('inf')):
+        raise ValueError('image_area %r must be finite and positive' % image_area)
+    return PyramidRoiAlignFn.apply(boxes.detach(), maps[0], maps[1], maps[2], maps[3], pool, image_area)
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -76,7 +76,8 @@ const char* sdn_last_error(void);
  * sdn_segm_labels_from_colors, sdn_segm_confusion added; 19: sdn_segm_train_batch added; 20: sdn_segm_loss_fwd,
  * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added; still 20: sdn_encode_maps,
  * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added; still 20: sdn_mrcnn_loss_workspace_bytes,
- * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added -- new entry
+ * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
+ * sdn_pyramid_roi_align_bwd added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1042,6 +1043,25 @@ int sdn_crop_and_resize_fwd(const float* image, int B, int C, int H, int W, cons
                             int n, int crop_h, int crop_w, float extrapolation, float* crops, sdnStream stream);
 int sdn_crop_and_resize_bwd(const float* grads, const float* boxes, const int32_t* box_index, int n, int crop_h, int crop_w,
                             float* grads_image, int B, int C, int H, int W, sdnStream stream);
+/* Pyramid RoIAlign: pyramid_roi_align of geometric/maskrcnn/model.py:414-502 with log2 of :95-100 (csrc/pyramid_roi_align.hip).
+ * boxes fp32 [R, 4] = (y1, x1, y2, x2) normalised; maps[4]: P2 .. P5, each fp32 [C, H[l], W[l]] contiguous; image_area =
+ * float(image_shape[0] * image_shape[1]).  Box r is sampled from level clamp(rint(4 + log(sqrt(h * w) / (224 / sqrt(image_area))) /
+ * log(2)), 2, 5), computed in fp32 operation for operation as :445-457; a non-finite value (area <= 0, NaN) gives level 2, which is
+ * what the reference's CPU run yields through the x86 float-to-int conversion and the clamp.  The samples are those of
+ * sdn_crop_and_resize_fwd with crop_h = crop_w = pool (1 <= pool <= 32), bit for bit.
+ * _fwd, ONE launch: pooled fp32 [R, C, pool, pool] in BOX order (row r is box r: no sort, no gather) and levels int32 [R] (2 .. 5).
+ * _bwd, a zero fill and ONE scatter launch: grads fp32 [R, C, pool, pool]; grad_maps is one caller-owned allocation, 16-byte aligned,
+ * of `total` floats that holds the four maps' gradients, level l as [C, H[l], W[l]] at float offsets[l] (every offset a multiple of
+ * four) -- ask sdn_pyramid_roi_align_grad_floats.  The whole allocation is zeroed first, so levels without a box are all zero.  The
+ * scatter uses fp32 atomic adds (as sdn_crop_and_resize_bwd and the reference's CUDA kernel): the gradients are NOT bit-reproducible
+ * from run to run.  The boxes get no gradient (the reference detaches them, :473).  R = 0: _fwd launches nothing, _bwd still zeroes.
+ * SDN_EINVAL with a message for: NULL pointers with R > 0, C <= 0, a level with H or W <= 0, pool outside [1, 32], image_area not
+ * finite or <= 0, C * H * W of a level or C * pool * pool not below 2^31.  Nothing is copied to the host. */
+int sdn_pyramid_roi_align_grad_floats(int C, const int* H, const int* W, size_t* offsets, size_t* total);
+int sdn_pyramid_roi_align_fwd(const float* boxes, int R, const float* const* maps, const int* H, const int* W, int C, int pool,
+                              float image_area, float extrapolation, float* pooled, int32_t* levels, sdnStream stream);
+int sdn_pyramid_roi_align_bwd(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
+                              float image_area, float* grad_maps, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)

@@ -1,0 +1,172 @@
+#!/usr/bin/env python3
+"""Times the pyramid RoIAlign at the shapes of the reference's configuration (geometric/maskrcnn/config.py; the VKITTI overrides of
+maskrcnn/vkitti.py:30-41 change the class count only): a 1024 x 1024 image, P2 .. P5 at 1/4 .. 1/32 of it (256, 128, 64, 32
+pixels square), 256 channels; the classifier's call with POOL_SIZE 7 on POST_NMS_ROIS_INFERENCE = 1000 proposals and the mask
+head's with MASK_POOL_SIZE 14 on DETECTION_MAX_INSTANCES = 100 detections.  Prints one JSON line; per call shape
+  device_fwd_ms, device_fwdbwd_ms   maskrcnn.pyramid.pyramid_roi_align (one launch), and with backward (a zero fill and one launch)
+  loop_fwd_ms, loop_fwdbwd_ms       the reference's loop (model.py:445-500) written with this library's CropAndResizeFunction and
+                                    torch, in the same process: the level formula, per level any / nonzero / gather / crop, the
+                                    cats, the sort and the final gather; and with backward
+  *_launches                        kernels per call as torch.profiler counts them (null where the profiler is unavailable)
+  bytes                             what the call must move, from the shapes: forward the boxes, the pooled output and one read of
+                                    every tap; backward the incoming gradient, the zero fill and four atomic adds per sample
+Each figure: --inner calls inside one synchronised region of the host clock, divided by --inner; the median of --reps such
+regions, the forms alternating inside every repetition, after --warmup calls of each; *_spread is (min, max) over the repetitions.
+The loop waits for the device eight times per call; the device form never does.  Checks first that both forms give the same bits
+forward and the same gradients to 1e-5 of their largest magnitude."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, '3d-sdn_amd'), os.path.join(ROOT, '3d-sdn_amd', 'geometric')):
+    sys.path.insert(0, p)
+
+IMAGE_SHAPE = (1024, 1024, 3)
+C = 256
+SIDES = (256, 128, 64, 32)
+CALLS = {'classifier_pool7_R1000': (7, 1000), 'mask_pool14_R100': (14, 100)}
+
+
+def loop_form(inputs, pool_size, image_shape, crop):
+    """pyramid_roi_align of the reference under a current torch, without changing `inputs`"""
+    boxes = inputs[0].squeeze(0)
+    feature_maps = [m.squeeze(0) for m in inputs[1:]]
+    y1, x1, y2, x2 = boxes.chunk(4, dim=1)
+    h = y2 - y1
+    w = x2 - x1
+    image_area = torch.tensor([float(image_shape[0] * image_shape[1])], device=boxes.device)
+    ln2 = torch.log(torch.tensor([2.0], device=boxes.device))
+    roi_level = 4 + torch.log(torch.sqrt(h * w) / (224.0 / torch.sqrt(image_area))) / ln2
+    roi_level = roi_level.round().int()
+    roi_level = roi_level.clamp(2, 5)
+    pooled = []
+    box_to_level = []
+    for i, level in enumerate(range(2, 6)):
+        ix = roi_level == level
+        if not ix.any():
+            continue
+        ix = torch.nonzero(ix)[:, 0]
+        level_boxes = boxes[ix, :]
+        box_to_level.append(ix)
+        level_boxes = level_boxes.detach()
+        ind = torch.zeros(level_boxes.size()[0], device=boxes.device).int()
+        pooled.append(crop(pool_size, pool_size, 0)(feature_maps[i].unsqueeze(0), level_boxes, ind))
+    pooled = torch.cat(pooled, dim=0)
+    box_to_level = torch.cat(box_to_level, dim=0)
+    _, box_to_level = torch.sort(box_to_level)
+    return pooled[box_to_level, :, :]
+
+
+def region(fn, inner):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(inner):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3 / inner
+
+
+def count_launches(fn):
+    try:
+        from torch.profiler import ProfilerActivity, profile
+        fn()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            fn()
+            torch.cuda.synchronize()
+        n = sum(1 for e in prof.events() if str(getattr(e, 'device_type', '')).endswith('CUDA') and 'memcpy' not in e.name.lower()
+                and 'memset' not in e.name.lower())
+        return n or None
+    except Exception:   # noqa: BLE001
+        return None
+
+
+def counted_bytes(R, pool):
+    out = R * C * pool * pool * 4
+    maps = sum(C * s * s * 4 for s in SIDES)
+    return {'fwd': R * 16 + out + 4 * out + R * 4, 'bwd': R * 16 + out + maps + 4 * out, 'pooled': out, 'maps': maps}
+
+
+def draw_boxes(rs, R):
+    """proposal-like boxes: sides log-uniform over 16 .. 700 pixels, so that all four levels are used; none within 1e-3 of a level
+    boundary, where torch's log and the kernel's logf may round to different sides"""
+    boxes = np.zeros((0, 4), np.float32)
+    while len(boxes) < R:
+        h, w = np.exp(rs.uniform(np.log(16 / 1024), np.log(700 / 1024), (2, R)))
+        y1, x1 = rs.uniform(0, 1 - h), rs.uniform(0, 1 - w)
+        b = np.stack([y1, x1, y1 + h, x1 + w], 1).astype(np.float32).astype(np.float64)
+        v = 4 + np.log2(np.sqrt((b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])) / (224.0 / 1024.0))
+        boxes = np.concatenate([boxes, b[np.abs(v - np.floor(v) - 0.5) > 1e-3].astype(np.float32)])
+    return boxes[:R]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--reps', type=int, default=11)
+    ap.add_argument('--inner', type=int, default=30)
+    ap.add_argument('--warmup', type=int, default=10)
+    a = ap.parse_args()
+    from maskrcnn import pyramid
+    from maskrcnn.roialign.roi_align.crop_and_resize import CropAndResizeFunction
+    assert torch.cuda.is_available(), 'this tool measures on the GPU; there is no CPU form of it'
+    rs = np.random.RandomState(11)
+    maps = [torch.from_numpy(rs.randn(1, C, s, s).astype(np.float32)).cuda().requires_grad_() for s in SIDES]
+    res = {'image_shape': IMAGE_SHAPE, 'C': C, 'sides': SIDES, 'reps': a.reps, 'inner': a.inner, 'calls': {}}
+    for name, (pool, R) in CALLS.items():
+        boxes = torch.from_numpy(draw_boxes(rs, R)[None]).cuda()
+        inputs = [boxes] + maps
+        g = torch.from_numpy(rs.randn(R, C, pool, pool).astype(np.float32)).cuda()
+
+        def clear():
+            for m in maps:
+                m.grad = None
+
+        def device_fwd():
+            return pyramid.pyramid_roi_align(inputs, pool, IMAGE_SHAPE)
+
+        def loop_fwd():
+            return loop_form(inputs, pool, IMAGE_SHAPE, CropAndResizeFunction)
+
+        def device_fwdbwd():
+            clear()
+            device_fwd().backward(g)
+
+        def loop_fwdbwd():
+            clear()
+            loop_fwd().backward(g)
+
+        forms = {'device_fwd': device_fwd, 'loop_fwd': loop_fwd, 'device_fwdbwd': device_fwdbwd, 'loop_fwdbwd': loop_fwdbwd}
+        # the same result first
+        d, t = device_fwd(), loop_fwd()
+        assert torch.equal(d.view(torch.int32), t.view(torch.int32)), 'the two forms differ forward'
+        device_fwdbwd()
+        gd = [m.grad.clone() for m in maps]
+        loop_fwdbwd()
+        rels = [float((x - m.grad).abs().max() / m.grad.abs().max()) for x, m in zip(gd, maps)]
+        assert max(rels) <= 1e-5, rels
+        for fn in forms.values():
+            for _ in range(a.warmup):
+                fn()
+        samples = {k: [] for k in forms}
+        for _ in range(a.reps):
+            for k, fn in forms.items():   # alternating: what disturbs one form disturbs the other
+                samples[k].append(region(fn, a.inner))
+        r = {'pool': pool, 'R': R, 'bytes': counted_bytes(R, pool), 'gradient_max_difference_between_forms': rels}
+        for k, v in samples.items():
+            r[k + '_ms'] = round(statistics.median(v), 5)
+            r[k + '_spread'] = [round(min(v), 5), round(max(v), 5)]
+        for k, fn in forms.items():
+            r[k + '_launches'] = count_launches(fn)
+        res['calls'][name] = r
+    print(json.dumps(res))
+
+
+if __name__ == '__main__':
+    main()
