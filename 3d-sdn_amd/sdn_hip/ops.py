@@ -1812,6 +1812,99 @@ def pyramid_roi_align(boxes, maps, pool, image_area):
     return PyramidRoiAlignFn.apply(boxes.detach(), maps[0], maps[1], maps[2], maps[3], pool, image_area)
 
 
+PROPOSAL_MAX_PRE_NMS, PROPOSAL_MAX_ANCHORS, PROPOSAL_CHUNK = 8192, 1 << 24, 1024   # csrc/proposal_layer_check.h: PROP_MAX_PRE_NMS, PROP_MAX_ANCHORS, PROP_CHUNK
+
+
+def proposal_workspace_bytes(A, K, P):
+    """bytes of the workspace of sdn_proposal_layer, asked of the library"""
+    n = ctypes.c_size_t(0)
+    check(lib().sdn_proposal_layer_workspace_bytes(int(A), int(K), int(P), ctypes.byref(n)))
+    return n.value
+
+
+def _proposal_rows(t, name, cols):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if t.dim() == 3:
+        if t.shape[0] != 1:
+            raise ValueError('%s has batch %d; only 1 is supported, as in the reference ("Currently only supports batchsize 1", '
+                             'geometric/maskrcnn/model.py:358)' % (name, t.shape[0]))
+        rows = t[0]        # a view: nothing is copied, and the caller's tensor keeps its shape
+    else:
+        rows = t
+    if rows.dim() != 2 or rows.shape[1] != cols:
+        raise ValueError('%s must be fp32 [A, %d] or [1, A, %d], got %s' % (name, cols, cols, tuple(t.shape)))
+    return rows
+
+
+def proposal_layer(rpn_probs, rpn_bbox, anchors, std_dev, height, width, proposal_count, nms_threshold, pre_nms_limit=6000, strict=True):
+    """The reference's proposal_layer (geometric/maskrcnn/model.py:344-407, apply_box_deltas :307-328, clip_boxes :331-341) --
+    sdn_proposal_layer (include/sdn_hip.h): rpn_probs fp32 [A, 2] = (bg, fg) or [1, A, 2], rpn_bbox fp32 [A, 4] or [1, A, 4], anchors
+    fp32 [A, 4] = (y1, x1, y2, x2) in pixels, std_dev four floats, height and width of the image in pixels, proposal_count P,
+    pre_nms_limit 1 .. 8192, K = min(pre_nms_limit, A).  Returns
+
+        order    int32 [K]     the K anchors with the largest fg score, best first, equal scores lower index first
+        boxes_px fp32 [K, 4]   those anchors decoded and clipped, in pixels
+        keep     int32 [P]     positions in `order` of the boxes the NMS keeps, -1 behind count
+        count    int32 [1]
+        rois     fp32 [P, 4]   boxes_px[keep] / (height, width, height, width), +0.0 behind count
+
+    strict=True suppresses on IoU > nms_threshold (the reference's CUDA rule), strict=False on >= (its CPU rule).  No result carries a
+    gradient: the reference detaches the boxes at the only place that differentiates past them (:473), and detection_target_layer
+    takes .data.  Nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape or size or a non-contiguous
+    tensor ValueError, a CPU tensor NotImplementedError: there is no torch form."""
+    probs = _proposal_rows(rpn_probs, 'rpn_probs', 2)
+    deltas = _proposal_rows(rpn_bbox, 'rpn_bbox', 4)
+    if not isinstance(anchors, torch.Tensor):
+        raise TypeError('anchors must be a torch.Tensor, got %r' % (type(anchors),))
+    if anchors.dim() != 2 or anchors.shape[1] != 4:
+        raise ValueError('anchors must be fp32 [A, 4], got %s' % (tuple(anchors.shape),))
+    A = anchors.shape[0]
+    if A == 0:
+        raise ValueError('no anchors: A = 0')
+    if A >= PROPOSAL_MAX_ANCHORS:
+        raise ValueError('A = %d; fewer than 2^24 anchors are supported' % A)
+    if probs.shape[0] != A or deltas.shape[0] != A:
+        raise ValueError('rpn_probs has %d rows, rpn_bbox %d, anchors %d' % (probs.shape[0], deltas.shape[0], A))
+    P, limit = int(proposal_count), int(pre_nms_limit)
+    if limit < 1 or limit > PROPOSAL_MAX_PRE_NMS:
+        raise ValueError('pre_nms_limit %d; 1 to %d are supported' % (limit, PROPOSAL_MAX_PRE_NMS))
+    if P < 1:
+        raise ValueError('proposal_count %d; at least 1' % P)
+    if P > limit:
+        raise ValueError('proposal_count %d exceeds pre_nms_limit %d' % (P, limit))
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError('image %d x %d' % (height, width))
+    std = [float(v) for v in std_dev]
+    if len(std) != 4:
+        raise ValueError('std_dev must hold four values, got %d' % len(std))
+    named = (('rpn_probs', probs), ('rpn_bbox', deltas), ('anchors', anchors))
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+    for name, t in named:
+        if not t.is_cuda:
+            raise NotImplementedError('%s is on %s; the proposal layer only runs on the GPU' % (name, t.device))
+        if t.device != probs.device:
+            raise ValueError('%s is on %s, rpn_probs on %s' % (name, t.device, probs.device))
+    K = min(limit, A)
+    dev = probs.device
+    with torch.cuda.device(dev):
+        order = torch.empty(K, dtype=torch.int32, device=dev)
+        boxes_px = torch.empty(K, 4, dtype=torch.float32, device=dev)
+        keep = torch.empty(P, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        rois = torch.empty(P, 4, dtype=torch.float32, device=dev)
+        ws = torch.empty(proposal_workspace_bytes(A, K, P), dtype=torch.uint8, device=dev)
+        check(lib().sdn_proposal_layer(ptr(probs.detach()), ptr(deltas.detach()), ptr(anchors.detach()), A, (ctypes.c_float * 4)(*std), height,
+                                       width, K, P, float(nms_threshold), int(bool(strict)), ptr(order), ptr(boxes_px), ptr(keep), ptr(count),
+                                       ptr(rois), ptr(ws), ws.numel(), stream()))
+    return order, boxes_px, keep, count, rois
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

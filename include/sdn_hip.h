@@ -77,7 +77,7 @@ const char* sdn_last_error(void);
  * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added; still 20: sdn_encode_maps,
  * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added; still 20: sdn_mrcnn_loss_workspace_bytes,
  * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
- * sdn_pyramid_roi_align_bwd added -- new entry
+ * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1062,6 +1062,27 @@ int sdn_pyramid_roi_align_fwd(const float* boxes, int R, const float* const* map
                               float image_area, float extrapolation, float* pooled, int32_t* levels, sdnStream stream);
 int sdn_pyramid_roi_align_bwd(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
                               float image_area, float* grad_maps, sdnStream stream);
+/* Proposal layer: proposal_layer of geometric/maskrcnn/model.py:344-407 with apply_box_deltas (:307-328) and clip_boxes (:331-341)
+ * (csrc/proposal_layer.hip).  rpn_probs fp32 [A, 2] = (bg, fg); rpn_bbox fp32 [A, 4]; anchors fp32 [A, 4] = (y1, x1, y2, x2) in pixels;
+ * std_dev: four floats in HOST memory, read during the call; 1 <= K <= min(A, 8192) anchors enter the NMS (the caller passes
+ * K = min(pre_nms_limit, A)), 1 <= P <= 8192 proposals leave it; 1 <= A < 2^24.
+ *  1. The K anchors with the largest rpn_probs[:, 1], best first, equal scores lower index first: torch.sort(descending=True,
+ *     stable=True), NaN above +inf.  An exact radix select finds the K-th score; the column is read in place, nothing sorts all A.
+ *  2. Decode and clip of those K rows in fp32, operation by operation as :370, :313-326, :336-340 (no FMA contraction; expf is the only
+ *     operation that can differ from the reference's CPU run); a NaN coordinate stays NaN, as torch.clamp leaves it.
+ *  3. Greedy NMS in score order with sdn_nms's own pair test (+1 pixel convention; strict 1: IoU > nms_threshold, 0: >=), stopped once P
+ *     boxes are kept: keep equals the first P entries sdn_nms keeps on the same boxes.
+ *  4. rois[r] = boxes_px[keep[r]] / (height, width, height, width), one IEEE division per coordinate (:402).
+ * Results, all DEVICE memory: order int32 [K] (anchor indices), boxes_px fp32 [K, 4], keep int32 [P] (positions in `order`; -1 behind
+ * *count), count int32 [1], rois fp32 [P, 4] (+0.0 behind *count).  Every element is written: nothing needs clearing.  Nothing is
+ * differentiable (the reference detaches the boxes where it differentiates past them, :473).  Workspace: query first; 16-byte aligned,
+ * as boxes_px and rois.  Two calls on the same inputs give the same bits.  Nothing is copied to the host, every launch goes to
+ * `stream`.  SDN_EINVAL with a message, before any launch, for sizes outside the ranges above, height or width < 1, NULL or misaligned
+ * pointers and a workspace that is too small. */
+int sdn_proposal_layer_workspace_bytes(int A, int K, int P, size_t* out);
+int sdn_proposal_layer(const float* rpn_probs, const float* rpn_bbox, const float* anchors, int A, const float* std_dev, int height,
+                       int width, int K, int P, float nms_threshold, int strict, int32_t* order, float* boxes_px, int32_t* keep,
+                       int32_t* count, float* rois, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
