@@ -25,6 +25,7 @@
 // Integer atomics build the histograms and hand out compaction slots; both are order-independent in what they produce, so two runs
 // give the same bits.  Every launch goes to the caller's stream; nothing is read back.
 #include "nms_mask.h"
+#include "prop_device.h"
 #include "proposal_layer_check.h"
 #include "rank_select.h"
 #include "sdn_common.h"
@@ -186,9 +187,6 @@ struct PropDecode {
     float* areas;            // [K]
 };
 
-// torch.clamp: NaN stays NaN (fminf / fmaxf would drop it)
-__device__ __forceinline__ float prop_clamp(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }
-
 __global__ __launch_bounds__(PROP_SORT_THREADS) void k_prop_sort(const PropDecode D)
 {
     __shared__ uint64_t s[PROP_MAX_PRE_NMS];
@@ -242,20 +240,6 @@ __global__ __launch_bounds__(64) void k_prop_mask(const float4* __restrict__ box
     __shared__ float4 cb[64];
     __shared__ float ca[64];
     nms_mask_block(boxes, areas, n, thresh, mask, nb, strict, cb, ca);
-}
-
-__device__ __forceinline__ unsigned long long prop_uniform64(unsigned long long v)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
-    return ((unsigned long long)hi << 32) | lo;
-}
-
-__device__ __forceinline__ unsigned long long prop_lane64(unsigned long long v, int src)
-{
-    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, src);
-    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 constexpr int PROP_MAX_WORDS = PROP_MAX_PRE_NMS / 64;

@@ -13,8 +13,11 @@
 //               fastest: the box's C * pool^2 outputs are contiguous, so the stores are coalesced, and the taps of one box fall into
 //               a window of a few dozen pixels per channel.
 //   k_pra_zero  16-byte stores over the one allocation that holds the four maps' gradients.
-//   k_pra_bwd   the same table; fp32 atomic adds into the box's level, as k_crop_bwd and the reference's CUDA kernel.  Levels without
-//               a box stay all zero.  The order of the adds is not fixed, so the gradients are not bit-reproducible from run to run.
+//   k_pra_bwd   the same table.  A box's contributions are summed in fp64 in an LDS window of the level's map, a few channels at a time,
+//               and every touched pixel then takes one fp32 atomic add per box (a window of more than PRA_BWD_CELLS pixels keeps
+//               the direct fp32 atomic adds of k_crop_bwd and the reference's CUDA kernel: few samples fall on each of its pixels).
+//               Levels without a box stay all zero.  The order of the adds is not fixed, so the gradients are not bit-reproducible
+//               from run to run; with one add per box and pixel they stay within a few ulp of the exact sum.
 //
 // A non-finite level value (a box of area <= 0, NaN) gives level 2: pyramid_roi_align_check.h, pra_level_of.
 #include "crop_sample.h"
@@ -41,7 +44,7 @@ struct PraTable {
     int* inside;
 };
 
-// the dynamic LDS, carved with the 16-byte entries first; nothing static lies in front of it
+// the dynamic LDS, carved with the 16-byte entries first; it is declared 16-byte aligned, whatever static LDS a kernel adds
 __device__ __forceinline__ PraTable pra_table(unsigned char* lds, int pp)
 {
     PraTable t;
@@ -124,39 +127,101 @@ __global__ __launch_bounds__(PRA_THREADS) void k_pra_zero(float4* __restrict__ p
     for (size_t i = (size_t)blockIdx.x * PRA_THREADS + threadIdx.x; i < n4; i += stride) p[i] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
 }
 
+constexpr int PRA_BWD_CELLS = 4096;   // fp64 cells of the backward's LDS window: 32 KiB
+
+// The rows (or columns) of the map that the box's samples can touch along one axis: axis_in is linear in the sample index, so its
+// values at the first and the last sample bound all of them; a sample that is inside (axis_inside) has floor and ceil in [0, extent - 1].
+// False when no sample can be inside.  fmaxf / fminf drop a NaN end, which only widens the range.
+__device__ __forceinline__ bool pra_axis_range(float a1, float a2, int extent, int pool, int* first, int* last)
+{
+    const float e0 = axis_in(a1, a2, extent, pool, 0), e1 = axis_in(a1, a2, extent, pool, pool - 1);
+    const float lo = fmaxf(fminf(e0, e1), 0.0f), hi = fminf(fmaxf(e0, e1), (float)(extent - 1));
+    if (!(lo <= hi)) return false;
+    *first = (int)floorf(lo);
+    *last = (int)ceilf(hi);
+    return true;
+}
+
 __global__ __launch_bounds__(PRA_THREADS) void k_pra_bwd(const PraParams P)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char pra_lds[];
+    __shared__ double acc[PRA_BWD_CELLS];
     const int pp = P.pool * P.pool;
     const PraTable t = pra_table(pra_lds, pp);
     const int r = blockIdx.x / P.chunks, chunk = blockIdx.x - r * P.chunks;
     const int l = pra_prepare(P, r, t);
     float* gmap = l == 0 ? P.gmap[0] : l == 1 ? P.gmap[1] : l == 2 ? P.gmap[2] : P.gmap[3];
-    const int HW = l == 0 ? P.H[0] * P.W[0] : l == 1 ? P.H[1] * P.W[1] : l == 2 ? P.H[2] * P.W[2] : P.H[3] * P.W[3];
+    const int H = l == 0 ? P.H[0] : l == 1 ? P.H[1] : l == 2 ? P.H[2] : P.H[3];
+    const int W = l == 0 ? P.W[0] : l == 1 ? P.W[1] : l == 2 ? P.W[2] : P.W[3];
+    const int HW = H * W;
     const int c0 = chunk * PRA_CHANNELS, nc = min(PRA_CHANNELS, P.C - c0);
     const float* g_in = P.grads + ((size_t)r * P.C + c0) * pp;
-    const int total = nc * pp;
-    const int dc = PRA_THREADS / pp, ds = PRA_THREADS - dc * pp;
-    int c = threadIdx.x / pp, s = threadIdx.x - c * pp;
-    for (int i = threadIdx.x; i < total; i += PRA_THREADS) {
-        if (t.inside[s]) {   // crop_and_resize.c:241-247
+    // The window of the level's map that this box touches.  Where it is small, many samples fall on each of its pixels, and a sum of
+    // that many fp32 atomic adds in whatever order they arrive strays from the exact gradient by more than the reference's own
+    // sequential fp32 sum does.  So the box's contributions are first summed in fp64 in LDS, a few channels at a time, and every
+    // touched pixel then receives ONE fp32 atomic add per box.  A window too large for the LDS has few samples per pixel and keeps
+    // the direct adds.
+    const float* box = P.boxes + 4 * (size_t)r;
+    int r0 = 0, r1 = 0, q0 = 0, q1 = 0;
+    if (!pra_axis_range(box[0], box[2], H, P.pool, &r0, &r1) || !pra_axis_range(box[1], box[3], W, P.pool, &q0, &q1)) return;   // no sample inside
+    const int wh = r1 - r0 + 1, ww = q1 - q0 + 1, cells = wh * ww;   // 1 <= wh <= H, 1 <= ww <= W
+    if (cells > PRA_BWD_CELLS) {
+        const int total = nc * pp;
+        const int dc = PRA_THREADS / pp, ds = PRA_THREADS - dc * pp;
+        int c = threadIdx.x / pp, s = threadIdx.x - c * pp;
+        for (int i = threadIdx.x; i < total; i += PRA_THREADS) {
+            if (t.inside[s]) {   // crop_and_resize.c:241-247
+                const int4 o = t.taps[s];
+                const float2 w = t.lerp[s];
+                float* p = gmap + (size_t)(c0 + c) * HW;
+                const float g = g_in[i];
+                const float dtop = (1.0f - w.y) * g;
+                unsafeAtomicAdd(p + o.x, (1.0f - w.x) * dtop);
+                unsafeAtomicAdd(p + o.y, w.x * dtop);
+                const float dbottom = w.y * g;
+                unsafeAtomicAdd(p + o.z, (1.0f - w.x) * dbottom);
+                unsafeAtomicAdd(p + o.w, w.x * dbottom);
+            }
+            c += dc;
+            s += ds;
+            if (s >= pp) {
+                s -= pp;
+                c++;
+            }
+        }
+        return;
+    }
+    const int group = min(nc, PRA_BWD_CELLS / cells);   // channels per pass, at least 1
+    const int origin = r0 * W + q0;
+    for (int cb = 0; cb < nc; cb += group) {
+        const int gc = min(group, nc - cb), used = gc * cells;
+        for (int i = threadIdx.x; i < used; i += PRA_THREADS) acc[i] = 0.0;
+        __syncthreads();
+        for (int i = threadIdx.x; i < gc * pp; i += PRA_THREADS) {
+            const int c = i / pp, s = i - c * pp;
+            if (!t.inside[s]) continue;
             const int4 o = t.taps[s];
             const float2 w = t.lerp[s];
-            float* p = gmap + (size_t)(c0 + c) * HW;
-            const float g = g_in[i];
-            const float dtop = (1.0f - w.y) * g;
-            unsafeAtomicAdd(p + o.x, (1.0f - w.x) * dtop);
-            unsafeAtomicAdd(p + o.y, w.x * dtop);
-            const float dbottom = w.y * g;
-            unsafeAtomicAdd(p + o.z, (1.0f - w.x) * dbottom);
-            unsafeAtomicAdd(p + o.w, w.x * dbottom);
+            // a tap (row, col) of the map is cell (row - r0, col - q0) of the window: inside it, since the sample is inside the map
+            const int top = (o.x - origin) / W, left = (o.x - origin) - top * W;
+            const int right = left + (o.y - o.x), down = (o.z - o.x) / W;   // 0 or 1 each
+            double* a = acc + c * cells + top * ww;
+            const float g = g_in[(size_t)(cb + c) * pp + s];
+            const float dtop = (1.0f - w.y) * g, dbottom = w.y * g;   // crop_and_resize.c:241-247
+            atomicAdd(a + left, (double)((1.0f - w.x) * dtop));
+            atomicAdd(a + right, (double)(w.x * dtop));
+            atomicAdd(a + down * ww + left, (double)((1.0f - w.x) * dbottom));
+            atomicAdd(a + down * ww + right, (double)(w.x * dbottom));
         }
-        c += dc;
-        s += ds;
-        if (s >= pp) {
-            s -= pp;
-            c++;
+        __syncthreads();
+        for (int i = threadIdx.x; i < used; i += PRA_THREADS) {
+            const float v = (float)acc[i];
+            if (v == 0.0f) continue;   // an untouched pixel receives nothing
+            const int c = i / cells, cell = i - c * cells;
+            const int row = cell / ww, col = cell - row * ww;
+            unsafeAtomicAdd(gmap + (size_t)(c0 + cb + c) * HW + (size_t)(r0 + row) * W + (q0 + col), v);
         }
+        __syncthreads();
     }
 }
 

@@ -1905,6 +1905,106 @@ def proposal_layer(rpn_probs, rpn_bbox, anchors, std_dev, height, width, proposa
     return order, boxes_px, keep, count, rois
 
 
+DETECTION_MAX_ROIS, DETECTION_MAX_INSTANCES = 8192, 8192   # csrc/detection_layer_check.h: DET_MAX_ROIS, DET_MAX_INSTANCES
+
+
+def detection_workspace_bytes(N, C, D):
+    """bytes of the workspace of sdn_detection_layer, asked of the library"""
+    n = ctypes.c_size_t(0)
+    check(lib().sdn_detection_layer_workspace_bytes(int(N), int(C), int(D), ctypes.byref(n)))
+    return n.value
+
+
+def _four_floats(values, name):
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise TypeError('%s must be four host numbers; a tensor on %s would have to be read back' % (name, values.device))
+        values = values.tolist()
+    out = [float(v) for v in values]
+    if len(out) != 4:
+        raise ValueError('%s must hold four values, got %d' % (name, len(out)))
+    return out
+
+
+def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_confidence, nms_threshold, max_instances, roi_count=None,
+                    strict=True):
+    """The reference's refine_detections (geometric/maskrcnn/model.py:744-837, apply_box_deltas :307-328, clip_to_window :731-741) --
+    sdn_detection_layer (include/sdn_hip.h): rois fp32 [N, 4] = (y1, x1, y2, x2) normalised, probs fp32 [N, C], deltas fp32 [N, C, 4],
+    window four host numbers (y1, x1, y2, x2) in pixels, std_dev four floats, height and width of the image in pixels, min_confidence
+    (0 or None: no confidence test, :796), max_instances D; 1 <= N <= 8192, 1 <= D <= 8192.  roi_count: None, or an int32 [1] tensor on
+    the device: rows at or behind it are never detections (the count of proposals_padded, handed through unread).  Returns
+
+        class_ids  int32 [N]     first index of every row's maximum (a NaN is the maximum)
+        scores     fp32  [N]
+        boxes_px   fp32  [N, 4]  decoded, scaled, clipped to the window, rounded half to even
+        keep       int32 [D]     row of each detection, best score first, -1 behind count
+        count      int32 [1]
+        detections fp32  [D, 6]  (y1, x1, y2, x2, class_id, score), +0.0 behind count
+        boxes_norm fp32  [D, 4]  detections[:, :4] / (height, width, height, width), +0.0 behind count
+
+    strict=True suppresses on IoU > nms_threshold (the reference's CUDA rule), strict=False on >= (its CPU rule).  Where no row is valid
+    count is 0 (the reference raises).  No result carries a gradient.  Nothing is copied to the host.  A wrong type or dtype raises
+    TypeError, a wrong shape or size or a non-contiguous tensor ValueError, a CPU tensor NotImplementedError: there is no torch
+    form."""
+    named = (('rois', rois), ('probs', probs), ('deltas', deltas))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if rois.dim() != 2 or rois.shape[1] != 4:
+        raise ValueError('rois must be fp32 [N, 4], got %s' % (tuple(rois.shape),))
+    N = rois.shape[0]
+    if probs.dim() != 2 or probs.shape[0] != N:
+        raise ValueError('probs must be fp32 [N, C] with N = %d, got %s' % (N, tuple(probs.shape)))
+    C = probs.shape[1]
+    if deltas.dim() != 3 or tuple(deltas.shape) != (N, C, 4):
+        raise ValueError('deltas must be fp32 [N, C, 4] = %s, got %s' % ((N, C, 4), tuple(deltas.shape)))
+    if N < 1 or N > DETECTION_MAX_ROIS:
+        raise ValueError('N = %d; 1 to %d rois are supported' % (N, DETECTION_MAX_ROIS))
+    if C < 1:
+        raise ValueError('no classes: C = 0')
+    D = int(max_instances)
+    if D < 1 or D > DETECTION_MAX_INSTANCES:
+        raise ValueError('max_instances %d; 1 to %d are supported' % (D, DETECTION_MAX_INSTANCES))
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError('image %d x %d' % (height, width))
+    win, std = _four_floats(window, 'window'), _four_floats(std_dev, 'std_dev')
+    min_confidence = float(min_confidence) if min_confidence else 0.0
+    if roi_count is not None:
+        if not isinstance(roi_count, torch.Tensor):
+            raise TypeError('roi_count must be None or an int32 [1] tensor on the device, got %r' % (type(roi_count),))
+        if roi_count.dtype != torch.int32:
+            raise TypeError('roi_count must be %s, got %s' % (torch.int32, roi_count.dtype))
+        if roi_count.numel() != 1:
+            raise ValueError('roi_count must hold one element, got %s' % (tuple(roi_count.shape),))
+        named = named + (('roi_count', roi_count),)
+    for name, t in named[:3]:
+        if t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+    for name, t in named:
+        if not t.is_cuda:
+            raise NotImplementedError('%s is on %s; the detection layer only runs on the GPU' % (name, t.device))
+        if t.device != rois.device:
+            raise ValueError('%s is on %s, rois on %s' % (name, t.device, rois.device))
+    dev = rois.device
+    with torch.cuda.device(dev):
+        class_ids = torch.empty(N, dtype=torch.int32, device=dev)
+        scores = torch.empty(N, dtype=torch.float32, device=dev)
+        boxes_px = torch.empty(N, 4, dtype=torch.float32, device=dev)
+        keep = torch.empty(D, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        detections = torch.empty(D, 6, dtype=torch.float32, device=dev)
+        boxes_norm = torch.empty(D, 4, dtype=torch.float32, device=dev)
+        ws = torch.empty(detection_workspace_bytes(N, C, D), dtype=torch.uint8, device=dev)
+        check(lib().sdn_detection_layer(ptr(rois.detach()), ptr(probs.detach()), ptr(deltas.detach()), N, C, (ctypes.c_float * 4)(*win),
+                                        (ctypes.c_float * 4)(*std), height, width, min_confidence, float(nms_threshold), D, int(bool(strict)),
+                                        ptr(roi_count) if roi_count is not None else None, ptr(class_ids), ptr(scores), ptr(boxes_px),
+                                        ptr(keep), ptr(count), ptr(detections), ptr(boxes_norm), ptr(ws), ws.numel(), stream()))
+    return class_ids, scores, boxes_px, keep, count, detections, boxes_norm
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -77,7 +77,8 @@ const char* sdn_last_error(void);
  * sdn_segm_loss_bwd added; still 20: sdn_segm_ppm_pool, sdn_segm_ppm_fill, sdn_segm_ppm_fill_bwd, sdn_segm_ppm_pool_bwd added; still 20: sdn_encode_maps,
  * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added; still 20: sdn_mrcnn_loss_workspace_bytes,
  * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
- * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added -- new entry
+ * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
+ * sdn_detection_layer_workspace_bytes, sdn_detection_layer added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1083,6 +1084,31 @@ int sdn_proposal_layer_workspace_bytes(int A, int K, int P, size_t* out);
 int sdn_proposal_layer(const float* rpn_probs, const float* rpn_bbox, const float* anchors, int A, const float* std_dev, int height,
                        int width, int K, int P, float nms_threshold, int strict, int32_t* order, float* boxes_px, int32_t* keep,
                        int32_t* count, float* rois, void* workspace, size_t workspace_bytes, sdnStream stream);
+
+/* Detection layer: refine_detections of geometric/maskrcnn/model.py:744-837 with apply_box_deltas (:307-328) and clip_to_window
+ * (:731-741) (csrc/detection_layer.hip).  rois fp32 [N, 4] = (y1, x1, y2, x2) normalised; probs fp32 [N, C]; deltas fp32 [N, C, 4];
+ * window (y1, x1, y2, x2 in pixels) and std_dev: four floats each in HOST memory, read during the call; 1 <= N <= 8192, 1 <= C,
+ * 1 <= D <= 8192 (max_instances); roi_count: int32 [1] in DEVICE memory or NULL (= N): rows at or behind it are never detections.
+ *  1. Per row: class_id = the first index of the row's maximum (a NaN is the maximum, the first NaN wins: torch.max on the CPU),
+ *     score = that element; the class's deltas times std_dev, apply_box_deltas in normalised coordinates, times (height, width,
+ *     height, width), clamp to the window as torch.clamp (a NaN stays), round half to even -- fp32, operation by operation, no FMA
+ *     contraction; expf is the only operation that can differ from the reference's CPU run.
+ *  2. A row is valid if it lies below *roi_count, class_id > 0 and, unless min_confidence == 0 (:796), score >= min_confidence.
+ *  3. Per-class greedy NMS on the rounded boxes with sdn_nms's pair test (+1 pixel convention; strict 1: IoU > nms_threshold, 0: >=),
+ *     rows in descending score order, equal scores lower row first; of the rows kept, the best D by score, best first.  Computed as
+ *     one scan in that order over a pair mask that also requires equal class ids, stopped at D.
+ * Results, all DEVICE memory: class_ids int32 [N], scores fp32 [N], boxes_px fp32 [N, 4] (every row); keep int32 [D] (rows; -1 behind
+ * *count), count int32 [1], detections fp32 [D, 6] = (y1, x1, y2, x2, class_id, score) and boxes_norm fp32 [D, 4] = detections[:, :4]
+ * / (height, width, height, width), one IEEE division per coordinate (:1769); both +0.0 behind *count.  Where no row is valid *count
+ * is 0 (the reference raises).  Every element is written: nothing needs clearing.  Nothing is differentiable.  Workspace: query first;
+ * 16-byte aligned, as boxes_px and boxes_norm.  Two calls on the same inputs give the same bits.  Nothing is copied to the host, every
+ * launch goes to `stream`.  SDN_EINVAL with a message, before any launch, for sizes outside the ranges above, height or width < 1,
+ * NULL or misaligned pointers and a workspace that is too small. */
+int sdn_detection_layer_workspace_bytes(int N, int C, int D, size_t* out);
+int sdn_detection_layer(const float* rois, const float* probs, const float* deltas, int N, int C, const float* window,
+                        const float* std_dev, int height, int width, float min_confidence, float nms_threshold, int D, int strict,
+                        const int32_t* roi_count, int32_t* class_ids, float* scores, float* boxes_px, int32_t* keep, int32_t* count,
+                        float* detections, float* boxes_norm, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)

@@ -1,0 +1,43 @@
+#!/usr/bin/env python3
+"""Measures how far the map gradients of pyramid_roi_align lie from the float64 gradients of the fixture
+tests/golden/pyramid_roi_align_golden.npz over repeated backward runs: the order of the atomic adds differs from run to run, so one
+run says little.  Per case of tests/pyramid_roi_align_util.py prints the worst distance per level as a share of the fixture's gate
+and how many of --runs runs exceeded a gate.  On the GPU only."""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, '3d-sdn_amd'), os.path.join(ROOT, '3d-sdn_amd', 'geometric'), os.path.join(ROOT, 'tests')):
+    sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--runs', type=int, default=40)
+    a = ap.parse_args()
+    import pyramid_roi_align_util as u
+    from maskrcnn import pyramid
+    assert torch.cuda.is_available(), 'this tool measures on the GPU; there is no CPU form of it'
+    gold = np.load(u.GOLD)
+    for name in u.CASES:
+        c = u.draw_case(name)
+        want = [gold[name + '/grad64_%d' % l] for l in range(u.LEVELS)]
+        gate = gold[name + '/gate']
+        worst, over = np.zeros(u.LEVELS), 0
+        for _ in range(a.runs):
+            boxes = torch.from_numpy(c['boxes'].copy())[None].cuda()
+            maps = [torch.from_numpy(m.copy())[None].cuda().requires_grad_(True) for m in c['maps']]
+            pooled, _levels = pyramid.pyramid_levels([boxes] + maps, c['pool'], u.IMAGE_SHAPE)
+            pooled.backward(torch.from_numpy(c['grads'].copy()).cuda())
+            err = u.grad_error([m.grad[0].cpu().numpy() for m in maps], want)
+            worst = np.maximum(worst, err)
+            over += int((err > gate).any())
+        print('%-10s worst / gate %s   runs over a gate: %d of %d' % (name, ' '.join('%.3f' % v for v in worst / gate), over, a.runs), flush=True)
+
+
+if __name__ == '__main__':
+    main()
