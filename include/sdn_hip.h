@@ -240,9 +240,10 @@ int sdn_conv_gemm_phases(const float* in, int N, int IH, int IW, int Cip, float*
                          int precision, sdnStream stream);
 
 /* dw[r, t*Cc + c] += sum_{n,q} a(rows[n, q, r]) * b(gath[n, q*istride + d_t, c])   (autograd of the layers above wrt their
- * weights).  rows [N, QH, QW, Cr], gath [N, GH, GW, Cc], dw [Cr, ntaps*Cc] fp32 (zeroed by the caller).  splits: K slices
- * over the positions; workspace NULL: combined with float atomics; workspace of splits * Cr * ntaps*Cc floats: combined in
- * slice order (bit-reproducible). */
+ * weights).  rows [N, QH, QW, Cr], gath [N, GH, GW, Cc], dw [Cr, ntaps*Cc] fp32, ADDED TO in both modes (the caller zeroes it for a
+ * plain gradient; rows and channels of the padding receive sums of zeros and keep their values).  splits: K slices over the
+ * positions (at most one per 32-position step); workspace NULL: combined with float atomics; workspace of splits * Cr * ntaps*Cc
+ * floats: combined in slice order (bit-reproducible); one too small for the slices actually used is SDN_ENOMEM. */
 int sdn_conv_wgrad(const float* rows, const float* gath, float* dw, int N, int QH, int QW, int Cr, int GH, int GW, int Cc,
                    int istride, int ntaps, const int8_t* dy, const int8_t* dx, int pad_mode, int relu_rows,
                    int relu_gath, int splits, int precision, void* workspace, size_t workspace_bytes, sdnStream stream);
