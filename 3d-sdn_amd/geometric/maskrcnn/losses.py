@@ -9,7 +9,8 @@ geometric/maskrcnn/model.py:1004-1147) and their sum in MaskRCNN.train_epoch / v
 or `mrcnn_losses(...)['loss'].backward()` with the sum taken on the device.  The reference finds the contributing anchors and RoIs
 with four torch.nonzero calls, each of which waits for the device, and gathers through index tensors; here nothing crosses to the
 host.  The kernels are csrc/mrcnn_loss.hip behind sdn_hip.ops.mrcnn_loss; CPU tensors raise NotImplementedError and there is no
-torch form.  The network, detection_target_layer and build_rpn_targets stay the caller's.
+torch form.  detection_target_layer, the step that makes the head targets, is maskrcnn.detection_targets; its padded form marks the
+rows behind its count with class id -1, which the head losses here leave out.  The network and build_rpn_targets stay the caller's.
 """
 import torch
 

@@ -2005,6 +2005,113 @@ def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_con
     return class_ids, scores, boxes_px, keep, count, detections, boxes_norm
 
 
+# csrc/detection_targets_check.h: DT_MAX_ROIS, DT_MAX_TARGETS, DT_MAX_BOXES, DT_MAX_MASK_SIDE
+TARGETS_MAX_ROIS, TARGETS_MAX_PER_IMAGE, TARGETS_MAX_BOXES, TARGETS_MAX_MASK_SIDE = 8192, 8192, 128, 64
+
+
+def detection_targets_workspace_bytes(N, G, mask_h, mask_w, R, H, W):
+    """bytes of the workspace of sdn_detection_targets, asked of the library"""
+    n = ctypes.c_size_t(0)
+    check(lib().sdn_detection_targets_workspace_bytes(int(N), int(G), int(mask_h), int(mask_w), int(R), int(H), int(W), ctypes.byref(n)))
+    return n.value
+
+
+def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_per_image, positive_ratio, std_dev, mask_shape,
+                      use_mini_mask=True, roi_count=None):
+    """The reference's detection_target_layer for one image (geometric/maskrcnn/model.py:545-724, bbox_overlaps :508-542,
+    utils.box_refinement utils.py:92-113) -- sdn_detection_targets (include/sdn_hip.h): proposals fp32 [N, 4] = (y1, x1, y2, x2)
+    normalised, gt_class_ids int32 or int64 [G], gt_boxes fp32 [G, 4] normalised, gt_masks fp32 [G, mh, mw], keys fp32 [2, N] (the
+    randomness as data: row 0 orders the positives, row 1 the negatives, smallest first, equal keys lower row first), rois_per_image R,
+    positive_ratio in (0, 1], std_dev four positive floats, mask_shape (H, W) each 1 to 64; 1 <= N <= 8192, 1 <= G <= 128,
+    1 <= R <= 8192.  roi_count: None, or an int32 [1] tensor on the device: rows at or behind it are never sampled (the count of
+    proposals_padded, handed through unread).  Returns, positives first, then negatives:
+
+        rois             fp32  [R, 4]     the sampled proposals, +0.0 behind count
+        target_class_ids int32 [R]        the matched box's id, 0 for negatives, -1 behind count
+        target_deltas    fp32  [R, 4]     box_refinement / std_dev, +0.0 for negatives and behind count
+        target_mask      fp32  [R, H, W]  the matched mask cropped and rounded half to even, +0.0 for negatives and behind count
+        rows             int32 [R]        proposal row of every output row, -1 behind count
+        assign           int32 [R]        matched box among the G for positives, else -1
+        count            int32 [1]
+        n_pos            int32 [1]
+
+    use_mini_mask=True crops the roi re-expressed in the matched box's frame (:642-650), False the roi itself from a full-size mask.
+    Where there is no positive, or the crowd filter leaves no box (the reference raises), count is 0.  No result carries a gradient.
+    Nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape or size or a non-contiguous tensor
+    ValueError, a CPU tensor NotImplementedError: there is no torch form."""
+    named = (('proposals', proposals), ('gt_class_ids', gt_class_ids), ('gt_boxes', gt_boxes), ('gt_masks', gt_masks), ('keys', keys))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if proposals.dim() != 2 or proposals.shape[1] != 4:
+        raise ValueError('proposals must be fp32 [N, 4], got %s' % (tuple(proposals.shape),))
+    N = proposals.shape[0]
+    if N < 1 or N > TARGETS_MAX_ROIS:
+        raise ValueError('N = %d; 1 to %d proposals are supported' % (N, TARGETS_MAX_ROIS))
+    if gt_class_ids.dim() != 1:
+        raise ValueError('gt_class_ids must be [G], got %s' % (tuple(gt_class_ids.shape),))
+    G = gt_class_ids.shape[0]
+    if G < 1 or G > TARGETS_MAX_BOXES:
+        raise ValueError('G = %d; 1 to %d boxes are supported' % (G, TARGETS_MAX_BOXES))
+    if tuple(gt_boxes.shape) != (G, 4):
+        raise ValueError('gt_boxes must be fp32 [G, 4] = %s, got %s' % ((G, 4), tuple(gt_boxes.shape)))
+    if gt_masks.dim() != 3 or gt_masks.shape[0] != G or gt_masks.shape[1] < 1 or gt_masks.shape[2] < 1:
+        raise ValueError('gt_masks must be fp32 [G, mh, mw] with G = %d, got %s' % (G, tuple(gt_masks.shape)))
+    if tuple(keys.shape) != (2, N):
+        raise ValueError('keys must be fp32 [2, N] = %s, got %s' % ((2, N), tuple(keys.shape)))
+    R = int(rois_per_image)
+    if R < 1 or R > TARGETS_MAX_PER_IMAGE:
+        raise ValueError('rois_per_image %d; 1 to %d are supported' % (R, TARGETS_MAX_PER_IMAGE))
+    ratio = float(positive_ratio)
+    if not (0.0 < ratio <= 1.0):
+        raise ValueError('positive_ratio %r; it must lie in (0, 1]' % (positive_ratio,))
+    std = _four_floats(std_dev, 'std_dev')
+    if not all(v > 0 for v in std):
+        raise ValueError('std_dev must be positive, got %s' % (std,))
+    shape = [int(v) for v in mask_shape]
+    if len(shape) != 2 or not all(1 <= v <= TARGETS_MAX_MASK_SIDE for v in shape):
+        raise ValueError('mask_shape %s; two sides of 1 to %d are supported' % (tuple(shape), TARGETS_MAX_MASK_SIDE))
+    H, W = shape
+    if gt_class_ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError('gt_class_ids must be %s or %s, got %s' % (torch.int32, torch.int64, gt_class_ids.dtype))
+    if roi_count is not None:
+        if not isinstance(roi_count, torch.Tensor):
+            raise TypeError('roi_count must be None or an int32 [1] tensor on the device, got %r' % (type(roi_count),))
+        if roi_count.dtype != torch.int32:
+            raise TypeError('roi_count must be %s, got %s' % (torch.int32, roi_count.dtype))
+        if roi_count.numel() != 1:
+            raise ValueError('roi_count must hold one element, got %s' % (tuple(roi_count.shape),))
+        named = named + (('roi_count', roi_count),)
+    for name, t in named[:5]:
+        if name != 'gt_class_ids' and t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+    for name, t in named:
+        if not t.is_cuda:
+            raise NotImplementedError('%s is on %s; the detection targets only run on the GPU' % (name, t.device))
+        if t.device != proposals.device:
+            raise ValueError('%s is on %s, proposals on %s' % (name, t.device, proposals.device))
+    dev = proposals.device
+    mh, mw = gt_masks.shape[1], gt_masks.shape[2]
+    with torch.cuda.device(dev):
+        rois = torch.empty(R, 4, dtype=torch.float32, device=dev)
+        target_class_ids = torch.empty(R, dtype=torch.int32, device=dev)
+        target_deltas = torch.empty(R, 4, dtype=torch.float32, device=dev)
+        target_mask = torch.empty(R, H, W, dtype=torch.float32, device=dev)
+        rows = torch.empty(R, dtype=torch.int32, device=dev)
+        assign = torch.empty(R, dtype=torch.int32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        n_pos = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(detection_targets_workspace_bytes(N, G, mh, mw, R, H, W), dtype=torch.uint8, device=dev)
+        check(lib().sdn_detection_targets(ptr(proposals.detach()), ptr(gt_class_ids), ptr(gt_boxes.detach()), ptr(gt_masks.detach()),
+                                          ptr(keys.detach()), N, G, mh, mw, int(gt_class_ids.dtype == torch.int64),
+                                          ptr(roi_count) if roi_count is not None else None, R, ratio, (ctypes.c_float * 4)(*std), H, W,
+                                          int(bool(use_mini_mask)), ptr(rois), ptr(target_class_ids), ptr(target_deltas), ptr(target_mask),
+                                          ptr(rows), ptr(assign), ptr(count), ptr(n_pos), ptr(ws), ws.numel(), stream()))
+    return rois, target_class_ids, target_deltas, target_mask, rows, assign, count, n_pos
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -78,7 +78,8 @@ const char* sdn_last_error(void);
  * sdn_inst_index_workspace_bytes, sdn_inst_index_build, sdn_inst_index_rank added; still 20: sdn_mrcnn_loss_workspace_bytes,
  * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
  * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
- * sdn_detection_layer_workspace_bytes, sdn_detection_layer added -- new entry
+ * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
+ * sdn_detection_targets added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1110,6 +1111,38 @@ int sdn_detection_layer(const float* rois, const float* probs, const float* delt
                         const float* std_dev, int height, int width, float min_confidence, float nms_threshold, int D, int strict,
                         const int32_t* roi_count, int32_t* class_ids, float* scores, float* boxes_px, int32_t* keep, int32_t* count,
                         float* detections, float* boxes_norm, void* workspace, size_t workspace_bytes, sdnStream stream);
+
+/* Detection targets: detection_target_layer of geometric/maskrcnn/model.py:545-724 with bbox_overlaps (:508-542) and
+ * utils.box_refinement (utils.py:92-113) for one image (csrc/detection_targets.hip).  All pointers but std_dev are DEVICE memory.
+ * proposals fp32 [N, 4] = (y1, x1, y2, x2) normalised, 1 <= N <= 8192; gt_class_ids int32 [G] (ids_int64 0) or int64 [G] (1); gt_boxes
+ * fp32 [G, 4] normalised; gt_masks fp32 [G, mask_h, mask_w]; 1 <= G <= 128; keys fp32 [2, N]: the randomness, as data; roi_count int32
+ * [1] or NULL (= N): rows at or behind it are never sampled; R = TRAIN_ROIS_PER_IMAGE, 1 <= R <= 8192; positive_ratio in (0, 1];
+ * std_dev four positive floats in HOST memory, read during the call; (H, W) = MASK_SHAPE, each side 1 to 64.
+ *  1. IoU of every proposal with every box as bbox_overlaps computes it in fp32: compare-based max and min that hand a NaN on, a
+ *     clamp at 0 likewise, one IEEE division, no contraction.  If any id is negative, boxes with id < 0 are crowd boxes and only
+ *     boxes with id > 0 stay ground truth (:579-591); otherwise all G boxes stay, those with id 0 included.
+ *  2. A row's maximum over the ground truth and its FIRST index, a NaN being the maximum (torch.max).  Positive: maximum >= 0.5.
+ *     Negative: maximum < 0.5 and, with a crowd, the maximum over the crowd < 0.001.  A NaN maximum is neither.
+ *  3. The positives taken are the positive rows with the cap = int(R * positive_ratio) smallest keys[0], in key order; key order is the
+ *     usual monotone image of the float's bits, then lower row first.  With P of them taken, the negatives are the negative rows with
+ *     the min(int((1.0 / positive_ratio) * P - P), R - P) smallest keys[1], likewise; the count is Python's fp64 expression (:669-670).
+ *     Without a positive there is no negative either (:667); where the crowd filter leaves no box (the reference raises) *count is 0.
+ * Results, positives first, then negatives: rois fp32 [R, 4] (+0.0 behind *count); target_class_ids int32 [R] (the matched box's id,
+ * 0 for negatives, -1 behind *count: what sdn_mrcnn_loss_fwd leaves out); target_deltas fp32 [R, 4] = box_refinement / std_dev in fp32
+ * operation by operation, logf being the only operation whose last bit may differ from a CPU run (+0.0 for negatives and behind
+ * *count); target_mask fp32 [R, H, W]: crop_and_resize of the matched mask, rounded half to even -- with use_mini_mask the roi
+ * re-expressed in the matched box's frame (:642-650), otherwise the roi itself on a full-size mask (+0.0 for negatives and behind
+ * *count); rows int32 [R]: the proposal of every output row, -1 behind *count; assign int32 [R]: the matched box's index among the G,
+ * -1 for all but positives; count, n_pos int32 [1].  Every element is written: nothing needs clearing.  Nothing is differentiable.
+ * Two dependent launches on `stream`, no atomics: two calls on the same inputs give the same bits.  Nothing is copied to the host.
+ * Workspace: query first; 16-byte aligned, as rois and target_deltas.  SDN_EINVAL with a message, before any launch, for sizes outside
+ * the ranges above, NULL or misaligned pointers and a workspace that is too small. */
+int sdn_detection_targets_workspace_bytes(int N, int G, int mask_h, int mask_w, int R, int H, int W, size_t* out);
+int sdn_detection_targets(const float* proposals, const void* gt_class_ids, const float* gt_boxes, const float* gt_masks,
+                          const float* keys, int N, int G, int mask_h, int mask_w, int ids_int64, const int32_t* roi_count, int R,
+                          double positive_ratio, const float* std_dev, int H, int W, int use_mini_mask, float* rois,
+                          int32_t* target_class_ids, float* target_deltas, float* target_mask, int32_t* rows, int32_t* assign,
+                          int32_t* count, int32_t* n_pos, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
