@@ -10,7 +10,9 @@ or `mrcnn_losses(...)['loss'].backward()` with the sum taken on the device.  The
 with four torch.nonzero calls, each of which waits for the device, and gathers through index tensors; here nothing crosses to the
 host.  The kernels are csrc/mrcnn_loss.hip behind sdn_hip.ops.mrcnn_loss; CPU tensors raise NotImplementedError and there is no
 torch form.  detection_target_layer, the step that makes the head targets, is maskrcnn.detection_targets; its padded form marks the
-rows behind its count with class id -1, which the head losses here leave out.  The network and build_rpn_targets stay the caller's.
+rows behind its count with class id -1, which the head losses here leave out.  build_rpn_targets, the step that makes rpn_match and
+rpn_bbox, is maskrcnn.rpn_targets; its rpn_targets_padded returns them in the shapes taken here, so no argument comes from the host any
+more.  The network and the inputs of build_rpn_targets stay the caller's.
 """
 import torch
 

@@ -2112,6 +2112,97 @@ def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_pe
     return rois, target_class_ids, target_deltas, target_mask, rows, assign, count, n_pos
 
 
+# csrc/rpn_targets_check.h: RT_MAX_ANCHORS, RT_MAX_BOXES, RT_MAX_TARGETS
+RPN_TARGETS_MAX_ANCHORS, RPN_TARGETS_MAX_BOXES, RPN_TARGETS_MAX_PER_IMAGE = (1 << 24) - 1, 128, 8192
+
+
+def rpn_targets_workspace_bytes(A, G, T):
+    """bytes of the workspace of sdn_rpn_targets, asked of the library"""
+    n = ctypes.c_size_t(0)
+    check(lib().sdn_rpn_targets_workspace_bytes(int(A), int(G), int(T), ctypes.byref(n)))
+    return n.value
+
+
+def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_dev, gt_count=None):
+    """The reference's build_rpn_targets for one image (geometric/maskrcnn/model.py:1214-1322, compute_overlaps / compute_iou
+    utils.py:52-89) -- sdn_rpn_targets (include/sdn_hip.h): anchors fp64 [A, 4] = (y1, x1, y2, x2) in pixels, gt_class_ids int32 or
+    int64 [G], gt_boxes fp32 or int32 [G, 4] in pixels (widened exactly to fp64), keys fp32 [2, A] (the randomness as data: of too
+    many positives those with the smallest keys[0] stay, of too many negatives those with the smallest keys[1]; equal keys keep the
+    lower anchor), anchors_per_image T = RPN_TRAIN_ANCHORS_PER_IMAGE, std_dev = RPN_BBOX_STD_DEV, four positive numbers;
+    1 <= A < 2^24, 1 <= G <= 128, 2 <= T <= 8192.  gt_count: None, or an int32 [1] tensor on the device: boxes at or behind it are not
+    read.  Returns
+
+        rpn_match int32 [A]     1 positive, -1 negative, 0 neutral
+        rpn_bbox  fp32  [T, 4]  row k: the deltas of the k-th positive anchor in anchor order / std_dev, +0.0 behind n_pos
+        rows      int32 [T]     the anchor of every row, -1 behind n_pos
+        counts    int32 [2]     n_pos, n_neg after sampling
+
+    All arithmetic is fp64, only rpn_bbox is rounded to fp32 at the end.  Where the crowd filter leaves no box (the reference
+    raises) there is no positive.  No result carries a gradient.  Nothing is copied to the host.  A wrong type or dtype raises
+    TypeError, a wrong shape or size or a non-contiguous tensor ValueError, a CPU tensor NotImplementedError: there is no torch
+    form."""
+    named = (('anchors', anchors), ('gt_class_ids', gt_class_ids), ('gt_boxes', gt_boxes), ('keys', keys))
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    if anchors.dim() != 2 or anchors.shape[1] != 4:
+        raise ValueError('anchors must be fp64 [A, 4], got %s' % (tuple(anchors.shape),))
+    A = anchors.shape[0]
+    if A < 1 or A > RPN_TARGETS_MAX_ANCHORS:
+        raise ValueError('A = %d; 1 to %d anchors are supported' % (A, RPN_TARGETS_MAX_ANCHORS))
+    if gt_class_ids.dim() != 1:
+        raise ValueError('gt_class_ids must be [G], got %s' % (tuple(gt_class_ids.shape),))
+    G = gt_class_ids.shape[0]
+    if G < 1 or G > RPN_TARGETS_MAX_BOXES:
+        raise ValueError('G = %d; 1 to %d boxes are supported' % (G, RPN_TARGETS_MAX_BOXES))
+    if tuple(gt_boxes.shape) != (G, 4):
+        raise ValueError('gt_boxes must be [G, 4] = %s, got %s' % ((G, 4), tuple(gt_boxes.shape)))
+    if tuple(keys.shape) != (2, A):
+        raise ValueError('keys must be fp32 [2, A] = %s, got %s' % ((2, A), tuple(keys.shape)))
+    T = int(anchors_per_image)
+    if T < 2 or T > RPN_TARGETS_MAX_PER_IMAGE:
+        raise ValueError('anchors_per_image %d; 2 to %d are supported' % (T, RPN_TARGETS_MAX_PER_IMAGE))
+    std = _four_floats(std_dev, 'std_dev')
+    if not all(v > 0 for v in std):
+        raise ValueError('std_dev must be positive, got %s' % (std,))
+    if anchors.dtype != torch.float64:
+        raise TypeError('anchors must be %s (the reference\'s anchors are float64), got %s' % (torch.float64, anchors.dtype))
+    if gt_class_ids.dtype not in (torch.int32, torch.int64):
+        raise TypeError('gt_class_ids must be %s or %s, got %s' % (torch.int32, torch.int64, gt_class_ids.dtype))
+    if gt_boxes.dtype not in (torch.float32, torch.int32):
+        raise TypeError('gt_boxes must be %s or %s, got %s' % (torch.float32, torch.int32, gt_boxes.dtype))
+    if keys.dtype != torch.float32:
+        raise TypeError('keys must be %s, got %s' % (torch.float32, keys.dtype))
+    if gt_count is not None:
+        if not isinstance(gt_count, torch.Tensor):
+            raise TypeError('gt_count must be None or an int32 [1] tensor on the device, got %r' % (type(gt_count),))
+        if gt_count.dtype != torch.int32:
+            raise TypeError('gt_count must be %s, got %s' % (torch.int32, gt_count.dtype))
+        if gt_count.numel() != 1:
+            raise ValueError('gt_count must hold one element, got %s' % (tuple(gt_count.shape),))
+        named = named + (('gt_count', gt_count),)
+    for name, t in named[:4]:
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+    for name, t in named:
+        if not t.is_cuda:
+            raise NotImplementedError('%s is on %s; the RPN targets only run on the GPU' % (name, t.device))
+        if t.device != anchors.device:
+            raise ValueError('%s is on %s, anchors on %s' % (name, t.device, anchors.device))
+    dev = anchors.device
+    with torch.cuda.device(dev):
+        rpn_match = torch.empty(A, dtype=torch.int32, device=dev)
+        rpn_bbox = torch.empty(T, 4, dtype=torch.float32, device=dev)
+        rows = torch.empty(T, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int32, device=dev)
+        ws = torch.empty(rpn_targets_workspace_bytes(A, G, T), dtype=torch.uint8, device=dev)
+        check(lib().sdn_rpn_targets(ptr(anchors.detach()), ptr(gt_class_ids), ptr(gt_boxes.detach()), ptr(keys.detach()), A, G,
+                                    int(gt_class_ids.dtype == torch.int64), int(gt_boxes.dtype == torch.int32),
+                                    ptr(gt_count) if gt_count is not None else None, T, (ctypes.c_double * 4)(*std), ptr(rpn_match),
+                                    ptr(rpn_bbox), ptr(rows), ptr(counts), ptr(ws), ws.numel(), stream()))
+    return rpn_match, rpn_bbox, rows, counts
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -79,7 +79,7 @@ const char* sdn_last_error(void);
  * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
  * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
  * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
- * sdn_detection_targets added -- new entry
+ * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1143,6 +1143,34 @@ int sdn_detection_targets(const float* proposals, const void* gt_class_ids, cons
                           double positive_ratio, const float* std_dev, int H, int W, int use_mini_mask, float* rois,
                           int32_t* target_class_ids, float* target_deltas, float* target_mask, int32_t* rows, int32_t* assign,
                           int32_t* count, int32_t* n_pos, void* workspace, size_t workspace_bytes, sdnStream stream);
+
+/* RPN targets: build_rpn_targets of geometric/maskrcnn/model.py:1214-1322 with compute_overlaps / compute_iou (utils.py:52-89) for one
+ * image (csrc/rpn_targets.hip).  All pointers but std_dev are DEVICE memory.  anchors fp64 [A, 4] = (y1, x1, y2, x2) in pixels,
+ * 1 <= A < 2^24; gt_class_ids int32 [G] (ids_int64 0) or int64 [G] (1); gt_boxes fp32 [G, 4] (boxes_int32 0) or int32 [G, 4] (1) in
+ * pixels, widened exactly to fp64; 1 <= G <= 128; keys fp32 [2, A]: the randomness, as data; gt_count int32 [1] or NULL (= G): rows of
+ * gt_class_ids and gt_boxes at or behind it are not read; T = RPN_TRAIN_ANCHORS_PER_IMAGE, 2 <= T <= 8192; std_dev =
+ * RPN_BBOX_STD_DEV, four positive doubles in HOST memory, read during the call.  All arithmetic is fp64, operation for operation
+ * numpy's (no contraction, IEEE division), 0.3, 0.7 and 0.001 are compared in fp64; only rpn_bbox is rounded to fp32 at the end.
+ *  1. If any id is negative, boxes with id < 0 are crowd boxes and only boxes with id > 0 stay (:1235-1241); otherwise all boxes stay,
+ *     those with id 0 included.  IoU as compute_iou: maxima and minima that hand a NaN on, a clamp at 0 likewise.
+ *  2. An anchor's maximum over the boxes and its FIRST index (np.argmax: the first NaN is a maximum); its maximum over the crowd
+ *     (np.amax).  -1 where the maximum < 0.3 and, with a crowd, the crowd's maximum < 0.001 (:1265); then every box's best anchor --
+ *     the first anchor of its largest IoU, anchor 0 for a box that overlaps nothing -- becomes 1 (:1269); then 1 where the maximum
+ *     >= 0.7 (:1271).  Where no box stays (the reference raises) every maximum counts as 0 and there is no positive.
+ *  3. Of more than T / 2 positives the T / 2 with the smallest keys[0] stay and the others become 0; then of more than T - n_pos
+ *     negatives the T - n_pos with the smallest keys[1] stay (:1275-1288).  Key order is the usual monotone image of the float's bits;
+ *     equal keys keep the lower anchor.
+ * Results: rpn_match int32 [A]; rpn_bbox fp32 [T, 4]: row k holds the deltas of the k-th positive anchor in anchor order against the
+ * box of its arg-max (:1295-1320: a zero-height box gives -inf), divided by std_dev, +0.0 behind n_pos; rows int32 [T]: the anchor of
+ * every row, -1 behind n_pos; counts int32 [2] = (n_pos, n_neg) after sampling.  Every element is written: nothing needs clearing.
+ * Nothing is differentiable.  Eight dependent launches on `stream`, no [A, G] matrix, integer atomics only: two calls on the same
+ * inputs give the same bits; log is the only operation whose last bit may differ from a CPU run.  Nothing is copied to the host.
+ * Workspace: query first; 16-byte aligned, as anchors and rpn_bbox.  SDN_EINVAL with a message, before any launch, for sizes outside
+ * the ranges above, NULL or misaligned pointers and a workspace that is too small. */
+int sdn_rpn_targets_workspace_bytes(int A, int G, int T, size_t* out);
+int sdn_rpn_targets(const double* anchors, const void* gt_class_ids, const void* gt_boxes, const float* keys, int A, int G,
+                    int ids_int64, int boxes_int32, const int32_t* gt_count, int T, const double* std_dev, int32_t* rpn_match,
+                    float* rpn_bbox, int32_t* rows, int32_t* counts, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
