@@ -17,17 +17,19 @@
 //                wins: torch.max on the CPU) -- each lane walks every eighth class, so the wave reads 32 contiguous bytes per row
 //                and step instead of one float per lane 4 C bytes apart, and three exchanges inside the row's lanes combine the
 //                candidates by the same rule.  The row's first lane then takes the class's deltas times std_dev, apply_box_deltas
-//                in normalised coordinates, times (h, w, h, w), the clamp to the window (NaN stays NaN) and rintf (torch.round: half
-//                to even), all in fp32 operation by operation (this file is built without FMA contraction; expf is the only
-//                operation that can differ from the reference's CPU run).  Writes class_ids, scores, boxes_px for EVERY row and the row's 64-bit key (score image
-//                high, inverted row low; proposal_layer_check.h), 0 for a row that is no detection: at or behind roi_count,
-//                background, under the confidence.
-//   k_det_sort   ONE workgroup sorts the keys in LDS (bitonic, best first), finds the valid count M (the keys that are not 0) and
-//                gathers boxes, areas, class ids and rows of the first M places.  M is never known on the host.
+//                in normalised coordinates (prop_apply_deltas of prop_device.h), times (h, w, h, w), the clamp to the window (NaN
+//                stays NaN) and rintf (torch.round: half to even), all in fp32 operation by operation (this file is built without
+//                FMA contraction; the decode's expf() is the only operation that can differ from the reference's CPU run).  Writes
+//                class_ids, scores, boxes_px for EVERY row and the row's 64-bit key (score image high, inverted row low;
+//                proposal_layer_check.h), 0 for a row that is no detection: at or behind roi_count, background, under the
+//                confidence.
+//   k_det_sort   ONE workgroup sorts the keys in LDS (prop_sort_keys of prop_device.h: bitonic, best first), finds the valid count
+//                M (the keys that are not 0) and gathers boxes, areas, class ids and rows of the first M places.  M is never known
+//                on the host.
 //   k_det_mask   the pair mask over ceil(N / 64)^2 blocks; blocks at or past M leave at once.  suppresses() of nms_mask.h plus the
 //                class test.
-//   k_det_scan   ONE wave: k_prop_scan's word scan over the M rows, stopped at D; writes keep, count, detections and boxes_norm with
-//                their padding.
+//   k_det_scan   ONE wave: the word scan of k_prop_scan (nms_scan_words of nms_mask.h) over the M rows, stopped at D; writes keep,
+//                count, detections and boxes_norm with their padding.
 //
 // Four launches where a single fused one would be possible at N = 1000 (the whole mask, 1000 x 16 words, fits the LDS of one
 // workgroup): the mask is 16 x 16 = 256 independent blocks of 64 x 64 pair tests, 136 of them on or above the diagonal, which 136
@@ -90,15 +92,8 @@ __global__ __launch_bounds__(DET_ROW_THREADS) void k_det_rows(const DetRows R)
     const float* d = R.deltas + 4 * ((size_t)r * R.C + cls);
     const float ay1 = a[0], ax1 = a[1], ay2 = a[2], ax2 = a[3];
     const float d0 = d[0] * R.std_dev[0], d1 = d[1] * R.std_dev[1], d2 = d[2] * R.std_dev[2], d3 = d[3] * R.std_dev[3];   // :775
-    // apply_box_deltas, :313-326
-    float h = ay2 - ay1, w = ax2 - ax1;
-    float cy = ay1 + 0.5f * h, cx = ax1 + 0.5f * w;
-    cy = cy + d0 * h;
-    cx = cx + d1 * w;
-    h = h * expf(d2);
-    w = w * expf(d3);
-    float y1 = cy - 0.5f * h, x1 = cx - 0.5f * w;
-    float y2 = y1 + h, x2 = x1 + w;
+    const float4 box = prop_apply_deltas(ay1, ax1, ay2, ax2, d0, d1, d2, d3);   // apply_box_deltas, :313-326
+    float y1 = box.x, x1 = box.y, y2 = box.z, x2 = box.w;
     // :782
     y1 = y1 * R.height;
     x1 = x1 * R.width;
@@ -142,21 +137,7 @@ __global__ __launch_bounds__(DET_SORT_THREADS) void k_det_sort(const DetSort D)
     const int tid = threadIdx.x;
     for (int i = tid; i < D.S; i += DET_SORT_THREADS) s[i] = i < D.N ? D.keys[i] : 0ull;
     __syncthreads();
-    for (int k = 2; k <= D.S; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < D.S / 2; t += DET_SORT_THREADS) {
-                int i, l;
-                bool descending;
-                prop_bitonic_pair(t, j, k, &i, &l, &descending);
-                const uint64_t a = s[i], b = s[l];
-                if (descending ? a < b : a > b) {
-                    s[i] = b;
-                    s[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    prop_sort_keys(s, D.S, tid, DET_SORT_THREADS);
     if (tid == 0 && s[0] == 0ull) D.head[0] = 0;
     for (int r = tid; r < D.N; r += DET_SORT_THREADS) {
         const uint64_t key = s[r];
@@ -208,8 +189,6 @@ __global__ __launch_bounds__(64) void k_det_mask(const float4* __restrict__ boxe
     mask[(size_t)i * nb + blockIdx.x] = t;
 }
 
-constexpr int DET_SCAN_ROWS = 16;   // mask rows one batch of the scan fetches before it waits, as PROP_SCAN_ROWS
-
 struct DetScan {
     const unsigned long long* mask;   // [N, nb]
     const int32_t* head;              // [0] = M
@@ -230,58 +209,8 @@ __global__ __launch_bounds__(64) void k_det_scan(const DetScan S)
     __shared__ unsigned long long remv[DET_MAX_WORDS];
     __shared__ int s_keep[DET_MAX_INSTANCES];
     const int lane = threadIdx.x;
-    const int M = S.head[0], nb = S.nb, D = S.D;
-    const int nbm = prop_words(M);   // <= nb
-    const unsigned long long* mask = S.mask;
-    for (int w = lane; w < nbm; w += 64) remv[w] = 0ull;
-    __syncthreads();
-    int kept = 0;
-    unsigned long long diag = lane < M ? mask[(size_t)lane * nb] : 0ull;   // word 0 of the first 64 rows
-    for (int blk = 0; blk < nbm && kept < D; blk++) {
-        const int base = blk * 64, cnt = min(64, M - base);
-        unsigned long long alive = ~prop_uniform64(remv[blk]);
-        if (cnt < 64) alive &= (1ull << cnt) - 1ull;
-        unsigned long long kept_bits = 0ull;
-        const int kept_before = kept;
-        while (alive) {   // uniform: the lowest place still alive is kept and removes what it suppresses inside the word
-            const int b = __ffsll((long long)alive) - 1;
-            kept_bits |= 1ull << b;
-            alive &= ~(prop_lane64(diag, b) | (1ull << b));
-            if (++kept == D) break;
-        }
-        if ((kept_bits >> lane) & 1ull) s_keep[kept_before + __popcll(kept_bits & ((1ull << lane) - 1ull))] = base + lane;
-        // the next word's diagonal block does not depend on this word's decisions: it is fetched with the rows below, one wait for all
-        unsigned long long diag_next = 0ull;
-        if (blk + 1 < nbm && base + 64 + lane < M) diag_next = mask[(size_t)(base + 64 + lane) * nb + blk + 1];
-        if (kept < D) {
-            // OR the rows of this word's kept places into the words behind it: lane = word, DET_SCAN_ROWS rows' loads in flight at a time
-            const int j0 = blk + 1 + lane, j1 = j0 + 64;   // nbm <= 128: two words per lane reach the end
-            unsigned long long acc0 = 0ull, acc1 = 0ull, kb = kept_bits;
-            while (kb) {
-                unsigned long long t0[DET_SCAN_ROWS], t1[DET_SCAN_ROWS];
-#pragma unroll
-                for (int u = 0; u < DET_SCAN_ROWS; u++) {
-                    t0[u] = t1[u] = 0ull;
-                    if (kb) {
-                        const unsigned long long* row = mask + (size_t)(base + __ffsll((long long)kb) - 1) * nb;
-                        kb &= kb - 1ull;
-                        if (j0 < nbm) t0[u] = row[j0];
-                        if (j1 < nbm) t1[u] = row[j1];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < DET_SCAN_ROWS; u++) {
-                    acc0 |= t0[u];
-                    acc1 |= t1[u];
-                }
-            }
-            if (j0 < nbm) remv[j0] |= acc0;
-            if (j1 < nbm) remv[j1] |= acc1;
-        }
-        __syncthreads();
-        diag = diag_next;
-    }
-    __syncthreads();
+    const int D = S.D;
+    const int kept = nms_scan_words(S.mask, S.nb, S.head[0], D, remv, s_keep);   // M = head[0] rows take part
     if (lane == 0) *S.count = kept;
     for (int r = lane; r < D; r += 64) {
         float* det = S.detections + 6 * (size_t)r;

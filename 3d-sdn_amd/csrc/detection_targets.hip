@@ -13,7 +13,7 @@
 //                (this file is built without FMA contraction and with correctly rounded division), the first-index maximum over the
 //                ground truth (a NaN is the maximum: torch.max), the maximum over the crowd.  The row's class (positive: max >= 0.5;
 //                negative: max < 0.5 and crowd max < 0.001; neither), its sampling key, its number and its matched box make one 64-bit
-//                key (detection_targets_check.h); the bitonic network sorts them, best first: the positives by ascending sampling key,
+//                key (detection_targets_check.h); prop_sort_keys of prop_device.h sorts them, best first: the positives by ascending sampling key,
 //                then the negatives likewise.  Two lanes find where the classes end; P = min(cap, positives) and the negative count
 //                int((1 / ratio) P - P) of :669-670 in fp64 follow, and the lanes write rows, assign, rois, target_class_ids,
 //                target_deltas (box_refinement / std_dev, logf) and, for the mask kernel, the crop box of every positive (:642-650).
@@ -27,6 +27,7 @@
 
 #include "crop_sample.h"
 #include "detection_targets_check.h"
+#include "prop_device.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -127,21 +128,7 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_sample(const DtSample D)
         s[i] = key;
     }
     __syncthreads();
-    for (int k = 2; k <= D.S; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < D.S / 2; t += DT_THREADS) {
-                int i, l;
-                bool descending;
-                prop_bitonic_pair(t, j, k, &i, &l, &descending);
-                const uint64_t a = s[i], b = s[l];
-                if (descending ? a < b : a > b) {
-                    s[i] = b;
-                    s[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    prop_sort_keys(s, D.S, tid, DT_THREADS);
     // where the positives and the negatives end: at most one place each is the last of its class
     for (int i = tid; i < D.S; i += DT_THREADS) {
         const uint64_t c = dt_key_class(s[i]), next = i + 1 < D.S ? dt_key_class(s[i + 1]) : DT_NEITHER;

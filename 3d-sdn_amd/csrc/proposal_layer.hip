@@ -13,14 +13,14 @@
 //   k_prop_compact   the K survivors as 64-bit keys (image high, inverted index low): every score above T, and of the scores equal to
 //                    T the `need` lowest indices -- a tie's ordinal is the ties of the chunks before it, re-added, plus an ordered
 //                    prefix inside the chunk.  The keys are unique, so their order in the buffer does not matter.
-//   k_prop_sort      ONE workgroup sorts the keys in LDS (bitonic, best first: torch.sort(descending=True, stable=True)), writes
-//                    `order`, gathers the anchor and delta rows, decodes and clips operation by operation in fp32 (this file is built
-//                    without FMA contraction; expf is the only operation that can differ from the reference's CPU run) and writes
-//                    boxes_px and the areas.
+//   k_prop_sort      ONE workgroup sorts the keys in LDS (prop_sort_keys of prop_device.h: bitonic, best first:
+//                    torch.sort(descending=True, stable=True)), writes `order`, gathers the anchor and delta rows, decodes
+//                    (prop_apply_deltas of prop_device.h) and clips operation by operation in fp32 (this file is built without FMA
+//                    contraction; the decode's expf() is the only operation that can differ from the reference's CPU run) and
+//                    writes boxes_px and the areas.
 //   k_prop_mask      the pair mask of raster_boxes.hip's NMS (nms_mask.h), over the K boxes.
-//   k_prop_scan      ONE wave walks the boxes word by word (64 boxes): the decisions inside a word come from the word's diagonal mask
-//                    block held in registers, the rows of the word's kept boxes are then ORed into the running "removed" bitmap with
-//                    independent loads.  It stops once P boxes are kept and writes keep, count and rois with their padding.
+//   k_prop_scan      ONE wave walks the boxes word by word (nms_scan_words of nms_mask.h, shared with detection_layer.hip) until P
+//                    are kept, and writes keep, count and rois with their padding.
 //
 // Integer atomics build the histograms and hand out compaction slots; both are order-independent in what they produce, so two runs
 // give the same bits.  Every launch goes to the caller's stream; nothing is read back.
@@ -193,21 +193,7 @@ __global__ __launch_bounds__(PROP_SORT_THREADS) void k_prop_sort(const PropDecod
     const int tid = threadIdx.x;
     for (int i = tid; i < D.N; i += PROP_SORT_THREADS) s[i] = i < D.K ? D.keys[i] : 0ull;   // 0 sorts behind every key
     __syncthreads();
-    for (int k = 2; k <= D.N; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < D.N / 2; t += PROP_SORT_THREADS) {
-                int i, l;
-                bool descending;
-                prop_bitonic_pair(t, j, k, &i, &l, &descending);
-                const uint64_t a = s[i], b = s[l];
-                if (descending ? a < b : a > b) {
-                    s[i] = b;
-                    s[l] = a;
-                }
-            }
-            __syncthreads();
-        }
-    }
+    prop_sort_keys(s, D.N, tid, PROP_SORT_THREADS);
     for (int r = tid; r < D.K; r += PROP_SORT_THREADS) {
         const uint32_t idx = prop_key_index(s[r]);
         D.order[r] = (int32_t)idx;
@@ -215,15 +201,8 @@ __global__ __launch_bounds__(PROP_SORT_THREADS) void k_prop_sort(const PropDecod
         const float* d = D.deltas + 4 * (size_t)idx;
         const float ay1 = a[0], ax1 = a[1], ay2 = a[2], ax2 = a[3];
         const float d0 = d[0] * D.std_dev[0], d1 = d[1] * D.std_dev[1], d2 = d[2] * D.std_dev[2], d3 = d[3] * D.std_dev[3];   // :370
-        // apply_box_deltas, :313-326
-        float h = ay2 - ay1, w = ax2 - ax1;
-        float cy = ay1 + 0.5f * h, cx = ax1 + 0.5f * w;
-        cy = cy + d0 * h;
-        cx = cx + d1 * w;
-        h = h * expf(d2);
-        w = w * expf(d3);
-        float y1 = cy - 0.5f * h, x1 = cx - 0.5f * w;
-        float y2 = y1 + h, x2 = x1 + w;
+        const float4 box = prop_apply_deltas(ay1, ax1, ay2, ax2, d0, d1, d2, d3);   // apply_box_deltas, :313-326
+        float y1 = box.x, x1 = box.y, y2 = box.z, x2 = box.w;
         // clip_boxes, :336-340
         y1 = prop_clamp(y1, 0.0f, D.height);
         x1 = prop_clamp(x1, 0.0f, D.width);
@@ -243,7 +222,6 @@ __global__ __launch_bounds__(64) void k_prop_mask(const float4* __restrict__ box
 }
 
 constexpr int PROP_MAX_WORDS = PROP_MAX_PRE_NMS / 64;
-constexpr int PROP_SCAN_ROWS = 16;   // mask rows one batch of the scan fetches before it waits: a word of object-like boxes keeps about ten
 
 // mask [K, nb] of k_prop_mask; boxes_px [K]; keep [P], count [1], rois [P]
 __global__ __launch_bounds__(64) void k_prop_scan(const unsigned long long* __restrict__ mask, const float4* __restrict__ boxes_px, int K, int nb,
@@ -253,55 +231,7 @@ __global__ __launch_bounds__(64) void k_prop_scan(const unsigned long long* __re
     __shared__ unsigned long long remv[PROP_MAX_WORDS];
     __shared__ int s_keep[PROP_MAX_PRE_NMS];
     const int lane = threadIdx.x;
-    for (int w = lane; w < nb; w += 64) remv[w] = 0ull;
-    __syncthreads();
-    int kept = 0;
-    unsigned long long diag = lane < K ? mask[(size_t)lane * nb] : 0ull;   // word 0 of the first 64 rows
-    for (int blk = 0; blk < nb && kept < P; blk++) {
-        const int base = blk * 64, cnt = min(64, K - base);
-        unsigned long long alive = ~prop_uniform64(remv[blk]);
-        if (cnt < 64) alive &= (1ull << cnt) - 1ull;
-        unsigned long long kept_bits = 0ull;
-        const int kept_before = kept;
-        while (alive) {   // uniform: the lowest box still alive is kept and removes what it suppresses inside the word
-            const int b = __ffsll((long long)alive) - 1;
-            kept_bits |= 1ull << b;
-            alive &= ~(prop_lane64(diag, b) | (1ull << b));
-            if (++kept == P) break;
-        }
-        if ((kept_bits >> lane) & 1ull) s_keep[kept_before + __popcll(kept_bits & ((1ull << lane) - 1ull))] = base + lane;
-        // the next word's diagonal block does not depend on this word's decisions: it is fetched with the rows below, one wait for all
-        unsigned long long diag_next = 0ull;
-        if (blk + 1 < nb && base + 64 + lane < K) diag_next = mask[(size_t)(base + 64 + lane) * nb + blk + 1];
-        if (kept < P) {
-            // OR the rows of this word's kept boxes into the words behind it: lane = word, PROP_SCAN_ROWS rows' loads in flight at a time
-            const int j0 = blk + 1 + lane, j1 = j0 + 64;   // nb <= 128: two words per lane reach the end
-            unsigned long long acc0 = 0ull, acc1 = 0ull, kb = kept_bits;
-            while (kb) {
-                unsigned long long t0[PROP_SCAN_ROWS], t1[PROP_SCAN_ROWS];
-#pragma unroll
-                for (int u = 0; u < PROP_SCAN_ROWS; u++) {
-                    t0[u] = t1[u] = 0ull;
-                    if (kb) {
-                        const unsigned long long* row = mask + (size_t)(base + __ffsll((long long)kb) - 1) * nb;
-                        kb &= kb - 1ull;
-                        if (j0 < nb) t0[u] = row[j0];
-                        if (j1 < nb) t1[u] = row[j1];
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < PROP_SCAN_ROWS; u++) {
-                    acc0 |= t0[u];
-                    acc1 |= t1[u];
-                }
-            }
-            if (j0 < nb) remv[j0] |= acc0;
-            if (j1 < nb) remv[j1] |= acc1;
-        }
-        __syncthreads();
-        diag = diag_next;
-    }
-    __syncthreads();
+    const int kept = nms_scan_words(mask, nb, K, P, remv, s_keep);   // every row takes part: prop_words(K) == nb
     if (lane == 0) *count = kept;
     for (int r = lane; r < P; r += 64) {
         if (r < kept) {

@@ -1817,9 +1817,7 @@ PROPOSAL_MAX_PRE_NMS, PROPOSAL_MAX_ANCHORS, PROPOSAL_CHUNK = 8192, 1 << 24, 1024
 
 def proposal_workspace_bytes(A, K, P):
     """bytes of the workspace of sdn_proposal_layer, asked of the library"""
-    n = ctypes.c_size_t(0)
-    check(lib().sdn_proposal_layer_workspace_bytes(int(A), int(K), int(P), ctypes.byref(n)))
-    return n.value
+    return _workspace_bytes(lib().sdn_proposal_layer_workspace_bytes, A, K, P)
 
 
 def _proposal_rows(t, name, cols):
@@ -1880,16 +1878,8 @@ def proposal_layer(rpn_probs, rpn_bbox, anchors, std_dev, height, width, proposa
     if len(std) != 4:
         raise ValueError('std_dev must hold four values, got %d' % len(std))
     named = (('rpn_probs', probs), ('rpn_bbox', deltas), ('anchors', anchors))
-    for name, t in named:
-        if t.dtype != torch.float32:
-            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-    for name, t in named:
-        if not t.is_cuda:
-            raise NotImplementedError('%s is on %s; the proposal layer only runs on the GPU' % (name, t.device))
-        if t.device != probs.device:
-            raise ValueError('%s is on %s, rpn_probs on %s' % (name, t.device, probs.device))
+    _contiguous(named, fp32=('rpn_probs', 'rpn_bbox', 'anchors'))
+    _on_one_device(named, 'the proposal layer only runs on the GPU')
     K = min(limit, A)
     dev = probs.device
     with torch.cuda.device(dev):
@@ -1910,9 +1900,7 @@ DETECTION_MAX_ROIS, DETECTION_MAX_INSTANCES = 8192, 8192   # csrc/detection_laye
 
 def detection_workspace_bytes(N, C, D):
     """bytes of the workspace of sdn_detection_layer, asked of the library"""
-    n = ctypes.c_size_t(0)
-    check(lib().sdn_detection_layer_workspace_bytes(int(N), int(C), int(D), ctypes.byref(n)))
-    return n.value
+    return _workspace_bytes(lib().sdn_detection_layer_workspace_bytes, N, C, D)
 
 
 def _four_floats(values, name):
@@ -1924,6 +1912,48 @@ def _four_floats(values, name):
     if len(out) != 4:
         raise ValueError('%s must hold four values, got %d' % (name, len(out)))
     return out
+
+
+def _workspace_bytes(fn, *sizes):
+    """what a *_workspace_bytes entry point of the library answers for these sizes"""
+    n = ctypes.c_size_t(0)
+    check(fn(*[int(v) for v in sizes], ctypes.byref(n)))
+    return n.value
+
+
+def _are_tensors(named):
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+
+
+def _count_tensor(t, name):
+    """an optional count that is handed through unread: an int32 [1] tensor; _on_one_device then asks for the device"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be None or an int32 [1] tensor on the device, got %r' % (name, type(t)))
+    if t.dtype != torch.int32:
+        raise TypeError('%s must be %s, got %s' % (name, torch.int32, t.dtype))
+    if t.numel() != 1:
+        raise ValueError('%s must hold one element, got %s' % (name, tuple(t.shape)))
+
+
+def _contiguous(named, fp32=()):
+    """tensor by tensor: float32 where its name is in `fp32`, then contiguous"""
+    for name, t in named:
+        if name in fp32 and t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+        if not t.is_contiguous():
+            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+
+
+def _on_one_device(named, what):
+    """every tensor on the GPU and on the device of the first; `what` ends the refusal: 'the ... only runs on the GPU'"""
+    first, dev = named[0][0], named[0][1].device
+    for name, t in named:
+        if not t.is_cuda:
+            raise NotImplementedError('%s is on %s; %s' % (name, t.device, what))
+        if t.device != dev:
+            raise ValueError('%s is on %s, %s on %s' % (name, t.device, first, dev))
 
 
 def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_confidence, nms_threshold, max_instances, roi_count=None,
@@ -1947,9 +1977,7 @@ def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_con
     TypeError, a wrong shape or size or a non-contiguous tensor ValueError, a CPU tensor NotImplementedError: there is no torch
     form."""
     named = (('rois', rois), ('probs', probs), ('deltas', deltas))
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _are_tensors(named)
     if rois.dim() != 2 or rois.shape[1] != 4:
         raise ValueError('rois must be fp32 [N, 4], got %s' % (tuple(rois.shape),))
     N = rois.shape[0]
@@ -1971,23 +1999,10 @@ def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_con
     win, std = _four_floats(window, 'window'), _four_floats(std_dev, 'std_dev')
     min_confidence = float(min_confidence) if min_confidence else 0.0
     if roi_count is not None:
-        if not isinstance(roi_count, torch.Tensor):
-            raise TypeError('roi_count must be None or an int32 [1] tensor on the device, got %r' % (type(roi_count),))
-        if roi_count.dtype != torch.int32:
-            raise TypeError('roi_count must be %s, got %s' % (torch.int32, roi_count.dtype))
-        if roi_count.numel() != 1:
-            raise ValueError('roi_count must hold one element, got %s' % (tuple(roi_count.shape),))
+        _count_tensor(roi_count, 'roi_count')
         named = named + (('roi_count', roi_count),)
-    for name, t in named[:3]:
-        if t.dtype != torch.float32:
-            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-    for name, t in named:
-        if not t.is_cuda:
-            raise NotImplementedError('%s is on %s; the detection layer only runs on the GPU' % (name, t.device))
-        if t.device != rois.device:
-            raise ValueError('%s is on %s, rois on %s' % (name, t.device, rois.device))
+    _contiguous(named[:3], fp32=('rois', 'probs', 'deltas'))
+    _on_one_device(named, 'the detection layer only runs on the GPU')
     dev = rois.device
     with torch.cuda.device(dev):
         class_ids = torch.empty(N, dtype=torch.int32, device=dev)
@@ -2011,9 +2026,7 @@ TARGETS_MAX_ROIS, TARGETS_MAX_PER_IMAGE, TARGETS_MAX_BOXES, TARGETS_MAX_MASK_SID
 
 def detection_targets_workspace_bytes(N, G, mask_h, mask_w, R, H, W):
     """bytes of the workspace of sdn_detection_targets, asked of the library"""
-    n = ctypes.c_size_t(0)
-    check(lib().sdn_detection_targets_workspace_bytes(int(N), int(G), int(mask_h), int(mask_w), int(R), int(H), int(W), ctypes.byref(n)))
-    return n.value
+    return _workspace_bytes(lib().sdn_detection_targets_workspace_bytes, N, G, mask_h, mask_w, R, H, W)
 
 
 def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_per_image, positive_ratio, std_dev, mask_shape,
@@ -2040,9 +2053,7 @@ def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_pe
     Nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape or size or a non-contiguous tensor
     ValueError, a CPU tensor NotImplementedError: there is no torch form."""
     named = (('proposals', proposals), ('gt_class_ids', gt_class_ids), ('gt_boxes', gt_boxes), ('gt_masks', gt_masks), ('keys', keys))
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _are_tensors(named)
     if proposals.dim() != 2 or proposals.shape[1] != 4:
         raise ValueError('proposals must be fp32 [N, 4], got %s' % (tuple(proposals.shape),))
     N = proposals.shape[0]
@@ -2075,23 +2086,10 @@ def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_pe
     if gt_class_ids.dtype not in (torch.int32, torch.int64):
         raise TypeError('gt_class_ids must be %s or %s, got %s' % (torch.int32, torch.int64, gt_class_ids.dtype))
     if roi_count is not None:
-        if not isinstance(roi_count, torch.Tensor):
-            raise TypeError('roi_count must be None or an int32 [1] tensor on the device, got %r' % (type(roi_count),))
-        if roi_count.dtype != torch.int32:
-            raise TypeError('roi_count must be %s, got %s' % (torch.int32, roi_count.dtype))
-        if roi_count.numel() != 1:
-            raise ValueError('roi_count must hold one element, got %s' % (tuple(roi_count.shape),))
+        _count_tensor(roi_count, 'roi_count')
         named = named + (('roi_count', roi_count),)
-    for name, t in named[:5]:
-        if name != 'gt_class_ids' and t.dtype != torch.float32:
-            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-    for name, t in named:
-        if not t.is_cuda:
-            raise NotImplementedError('%s is on %s; the detection targets only run on the GPU' % (name, t.device))
-        if t.device != proposals.device:
-            raise ValueError('%s is on %s, proposals on %s' % (name, t.device, proposals.device))
+    _contiguous(named[:5], fp32=('proposals', 'gt_boxes', 'gt_masks', 'keys'))
+    _on_one_device(named, 'the detection targets only run on the GPU')
     dev = proposals.device
     mh, mw = gt_masks.shape[1], gt_masks.shape[2]
     with torch.cuda.device(dev):
@@ -2118,9 +2116,7 @@ RPN_TARGETS_MAX_ANCHORS, RPN_TARGETS_MAX_BOXES, RPN_TARGETS_MAX_PER_IMAGE = (1 <
 
 def rpn_targets_workspace_bytes(A, G, T):
     """bytes of the workspace of sdn_rpn_targets, asked of the library"""
-    n = ctypes.c_size_t(0)
-    check(lib().sdn_rpn_targets_workspace_bytes(int(A), int(G), int(T), ctypes.byref(n)))
-    return n.value
+    return _workspace_bytes(lib().sdn_rpn_targets_workspace_bytes, A, G, T)
 
 
 def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_dev, gt_count=None):
@@ -2142,9 +2138,7 @@ def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_de
     TypeError, a wrong shape or size or a non-contiguous tensor ValueError, a CPU tensor NotImplementedError: there is no torch
     form."""
     named = (('anchors', anchors), ('gt_class_ids', gt_class_ids), ('gt_boxes', gt_boxes), ('keys', keys))
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _are_tensors(named)
     if anchors.dim() != 2 or anchors.shape[1] != 4:
         raise ValueError('anchors must be fp64 [A, 4], got %s' % (tuple(anchors.shape),))
     A = anchors.shape[0]
@@ -2174,21 +2168,10 @@ def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_de
     if keys.dtype != torch.float32:
         raise TypeError('keys must be %s, got %s' % (torch.float32, keys.dtype))
     if gt_count is not None:
-        if not isinstance(gt_count, torch.Tensor):
-            raise TypeError('gt_count must be None or an int32 [1] tensor on the device, got %r' % (type(gt_count),))
-        if gt_count.dtype != torch.int32:
-            raise TypeError('gt_count must be %s, got %s' % (torch.int32, gt_count.dtype))
-        if gt_count.numel() != 1:
-            raise ValueError('gt_count must hold one element, got %s' % (tuple(gt_count.shape),))
+        _count_tensor(gt_count, 'gt_count')
         named = named + (('gt_count', gt_count),)
-    for name, t in named[:4]:
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-    for name, t in named:
-        if not t.is_cuda:
-            raise NotImplementedError('%s is on %s; the RPN targets only run on the GPU' % (name, t.device))
-        if t.device != anchors.device:
-            raise ValueError('%s is on %s, anchors on %s' % (name, t.device, anchors.device))
+    _contiguous(named[:4])
+    _on_one_device(named, 'the RPN targets only run on the GPU')
     dev = anchors.device
     with torch.cuda.device(dev):
         rpn_match = torch.empty(A, dtype=torch.int32, device=dev)

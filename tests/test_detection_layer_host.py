@@ -158,7 +158,7 @@ def test_the_kernels_are_built_without_fma_contraction_and_share_the_pair_test_a
     text = open(os.path.join(csrc, 'detection_layer.hip')).read()
     for h in ('nms_mask.h', 'prop_device.h', 'detection_layer_check.h'):
         assert '#include "%s"' % h in text
-    assert 'suppresses(' in text and not re.search(r'bool suppresses\(', text) and 'prop_clamp(' in text and 'prop_bitonic_pair(' in text
+    assert 'suppresses(' in text and not re.search(r'bool suppresses\(', text) and 'prop_clamp(' in text and 'prop_sort_keys(' in text
     assert 'rintf(' in text and not re.search(r'\broundf\(', text)                 # half to even
     assert 'expf(' in text and not re.search(r'__(expf|fdividef|frcp_r[a-z]|fdiv_r[a-z])\b', text)
     assert not re.search(r'\bf(min|max)f\(', text)                                 # they drop NaN: the clamp compares
@@ -166,8 +166,23 @@ def test_the_kernels_are_built_without_fma_contraction_and_share_the_pair_test_a
     assert 'hipLaunchCooperativeKernel' not in text and 'hipMemcpy' not in text and 'Synchronize' not in text
     shared = open(os.path.join(csrc, 'prop_device.h')).read()
     prop = open(os.path.join(csrc, 'proposal_layer.hip')).read()
-    for fn in ('prop_clamp', 'prop_uniform64', 'prop_lane64'):
+    for fn in ('prop_clamp', 'prop_uniform64', 'prop_lane64', 'prop_sort_keys', 'prop_apply_deltas'):
         assert len(re.findall(r'\b%s\(' % fn, shared)) == 1 and '#include "prop_device.h"' in prop
+    for f in (text, prop):                                                         # the decode and the sort are calls, not copies
+        assert len(re.findall(r'\bprop_apply_deltas\(', f)) == 1 and len(re.findall(r'\bprop_sort_keys\(', f)) == 1
+    # apply_box_deltas lives in the shared header: the same intrinsics are pinned there
+    assert len(re.findall(r'\bexpf\(', shared)) == 2 and '#include "proposal_layer_check.h"' in shared
+    for word in ('__expf', '__fdividef', 'fmaf', 'fminf', 'fmaxf', '__frcp_r', '__fdiv_r', 'atomic'):
+        assert word not in shared, word
+    assert len(re.findall(r'\bprop_bitonic_pair\(', shared)) == 1                 # the one device caller
+    for f in os.listdir(csrc):
+        if f.endswith('.hip'):
+            assert 'prop_bitonic_pair(' not in open(os.path.join(csrc, f)).read(), f
+    scan = open(os.path.join(csrc, 'nms_mask.h')).read()
+    assert len(re.findall(r'\bnms_scan_words\(', scan)) == 1 and re.search(r'\bint nms_scan_words\(', scan) and '#include "prop_device.h"' in scan
+    assert len(re.findall(r'\bNMS_SCAN_ROWS = 16;', scan)) == 1
+    for f in (text, prop):
+        assert len(re.findall(r'\bnms_scan_words\(', f)) == 1 and not re.search(r'\b(PROP|DET)_SCAN_ROWS\b', f)
 
 
 def test_the_constants_are_mirrored_and_the_workspace_comes_from_the_library():

@@ -191,9 +191,9 @@ def test_the_kernels_are_built_exactly_and_use_no_shortcut():
     assert '-ffp-contract=off' in re.search(r'^EXACT\s*:=\s*(.*)$', mk, flags=re.M).group(1) and '-fno-slp-vectorize' in mk
     assert '-fhip-fp32-correctly-rounded-divide-sqrt' in mk
     text = open(os.path.join(csrc, 'detection_targets.hip')).read()
-    for h in ('crop_sample.h', 'detection_targets_check.h'):
+    for h in ('crop_sample.h', 'detection_targets_check.h', 'prop_device.h'):
         assert '#include "%s"' % h in text
-    assert 'prop_bitonic_pair(' in text and 'det_argmax_takes(' in text and 'axis_in(' in text and 'axis_inside(' in text
+    assert 'prop_sort_keys(' in text and 'prop_bitonic_pair(' not in text and 'det_argmax_takes(' in text and 'axis_in(' in text and 'axis_inside(' in text
     assert 'dt_negatives_taken(' in text and 'dt_positive_cap(' in text
     assert 'rintf(' in text and not re.search(r'\broundf\(', text)                 # half to even
     assert 'logf(' in text and not re.search(r'__(logf|expf|fdividef|frcp_r[a-z]|fdiv_r[a-z]|fmaf_r[a-z])\b', text)

@@ -131,7 +131,7 @@ static void walk_scan_words()
         for (int blk = 0; blk < nb && ok; blk++) {
             std::vector<unsigned char> seen((size_t)nb, 0);
             for (int lane = 0; lane < 64; lane++) {
-                const int j0 = blk + 1 + lane, j1 = j0 + 64;   // k_prop_scan
+                const int j0 = blk + 1 + lane, j1 = j0 + 64;   // nms_scan_words (nms_mask.h)
                 if (j0 < nb) seen[(size_t)j0]++;
                 if (j1 < nb) seen[(size_t)j1]++;
             }
