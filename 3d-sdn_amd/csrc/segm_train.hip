@@ -97,9 +97,7 @@ __device__ __forceinline__ float sgt_pixel(const SegTrainParams& A, const SegTra
         const int32_t* yb = A.T + it.yb;
         const int32_t* k = A.T + it.yk + y * it.yksize;
         const int y0 = yb[2 * y] - ybase, yc = min(yb[2 * y + 1], it.yksize);
-        int acc = 1 << (SGT_BITS - 1);
-        for (int t = 0; t < yc; t++) acc += (int)plane[min(max(y0 + t, 0), rows - 1) * it.w + x] * k[t];
-        v = ti_clip8(acc >> SGT_BITS);
+        v = ti_resample_byte(plane + x, it.w, y0, yc, rows - 1, k);
     }
     return ((float)v - A.mean[ch]) / A.std[ch];
 }
@@ -181,9 +179,7 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_image(const SegTrain
                     v = row[min(x, W - 1)];
                 } else {
                     const int x0 = max(xb[2 * x], 0), xc = min(xb[2 * x + 1], xksize);
-                    int acc = 1 << (SGT_BITS - 1);
-                    for (int t = 0; t < xc; t++) acc += (int)row[min(x0 + t, W - 1)] * xk[x * xksize + t];
-                    v = ti_clip8(acc >> SGT_BITS);
+                    v = ti_resample_byte(row, 1, x0, xc, W - 1, xk + x * xksize);
                 }
                 s_rows[ch * SGT_PLANE_BYTES + (c0 + ry) * w + x] = (uint8_t)v;
             }

@@ -49,6 +49,15 @@ struct TrainItem {  // one row of the item table
 
 __device__ __forceinline__ int ti_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
+// One byte of a pass of Pillow's ImagingResample over 8-bit data (22-bit fixed point, rounded and clipped as Pillow stores it): the
+// taps first .. first + count of the bytes p[i * stride], the index held inside [0, last].
+__device__ __forceinline__ int ti_resample_byte(const uint8_t* p, int stride, int first, int count, int last, const int32_t* k)
+{
+    int acc = 1 << (TI_BITS - 1);
+    for (int t = 0; t < count; t++) acc += (int)p[min(max(first + t, 0), last) * stride] * k[t];
+    return ti_clip8(acc >> TI_BITS);
+}
+
 __device__ __forceinline__ int ti_wave_sum(int v)
 {
     for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);

@@ -2186,6 +2186,118 @@ def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_de
     return rpn_match, rpn_bbox, rows, counts
 
 
+# csrc/training_item_check.h: TRI_MAX_DIM, TRI_MAX_MINI, TRI_MAX_BOXES, TRI_PLAN_INTS
+TRAINING_ITEM_MAX_DIM, TRAINING_ITEM_MAX_MINI, TRAINING_ITEM_MAX_BOXES, TRAINING_ITEM_PLAN_INTS = 1024, 56, 128, 24
+
+
+def training_item_workspace_bytes(B, H, W, G):
+    """bytes of the workspace of sdn_training_item (G >= 1) and sdn_training_item_image (G = 0), asked of the library"""
+    return _workspace_bytes(lib().sdn_training_item_workspace_bytes, B, H, W, G)
+
+
+def _training_item_plan(plan_host, name='plan_host'):
+    plan_host = np.ascontiguousarray(plan_host, dtype=np.int32)
+    if plan_host.ndim != 1 or plan_host.size < TRAINING_ITEM_PLAN_INTS:
+        raise ValueError('%s must be int32 [n] with n >= %d, got %s' % (name, TRAINING_ITEM_PLAN_INTS, plan_host.shape))
+    return plan_host
+
+
+def training_item_image(frames_u8, plan_host):
+    """The image half of the Mask R-CNN training item for B frames of one size (utils.resize_image, utils.py:272-320, np.fliplr,
+    mold_image, geometric/maskrcnn/model.py:2196-2201) -- sdn_training_item_image (include/sdn_hip.h): frames_u8 uint8 [B, H, W, 3]
+    on the device, plan_host numpy int32 [n], the parameter block (maskrcnn.training_item.plan_block; csrc/training_item_check.h
+    lists its head).  It is uploaded here, in one copy.  Returns image fp32 [B, 3, M, M].  Nothing is copied to the host.  A wrong
+    type or dtype raises TypeError, a wrong shape ValueError, a CPU tensor NotImplementedError: there is no torch form."""
+    _are_tensors((('frames_u8', frames_u8),))
+    if frames_u8.dtype != torch.uint8:
+        raise TypeError('frames_u8 must be %s, got %s' % (torch.uint8, frames_u8.dtype))
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.shape[0] < 1:
+        raise ValueError('frames_u8 must be uint8 [B, H, W, 3], got %s' % (tuple(frames_u8.shape),))
+    plan_host = _training_item_plan(plan_host)
+    _contiguous((('frames_u8', frames_u8),))
+    _on_one_device((('frames_u8', frames_u8),), 'the training item only runs on the GPU')
+    B, H, W, _ = frames_u8.shape
+    M = int(plan_host[4])
+    if M < 1 or M > TRAINING_ITEM_MAX_DIM:
+        raise ValueError('IMAGE_MAX_DIM %d; 1 to %d is supported' % (M, TRAINING_ITEM_MAX_DIM))
+    dev = frames_u8.device
+    with torch.cuda.device(dev):
+        plan = torch.from_numpy(plan_host).to(dev)   # the one upload
+        ws = torch.empty(training_item_workspace_bytes(B, H, W, 0), dtype=torch.uint8, device=dev)
+        image = torch.empty(B, 3, M, M, dtype=torch.float32, device=dev)
+        check(lib().sdn_training_item_image(ptr(frames_u8), B, H, W, plan_host.ctypes.data, ptr(plan), plan_host.size, ptr(ws), ws.numel(),
+                                            ptr(image), stream()))
+    return image
+
+
+def training_item(frame_u8, inst_map, ids, plan_host, use_mini_mask, mini_shape):
+    """The Mask R-CNN training item of one image (load_image_gt, geometric/maskrcnn/model.py:1154-1211, with utils.resize_image,
+    resize_mask, extract_bboxes and minimize_mask, utils.py:26-49 and 272-353, mold_image, model.py:2196-2201, and the division of
+    :1790-1794) -- sdn_training_item (include/sdn_hip.h): frame_u8 uint8 [H, W, 3]; inst_map int32 [H, W] or uint8 [H, W, 3] (the id
+    of a pixel is r << 16 | g << 8 | b); ids int32 [G], 1 <= G <= 128; plan_host numpy int32 [n], the parameter block
+    (maskrcnn.training_item.plan_block), uploaded here in one copy; mini_shape (mh, mw), each 1 to 56, read with use_mini_mask.
+    Returns
+
+        image         fp32  [3, M, M]
+        gt_boxes_int  int32 [G, 4]      (y1, x1, y2, x2) in the padded, mirrored frame; zeros for an instance without a pixel
+        gt_boxes      fp32  [G, 4]
+        gt_boxes_norm fp32  [G, 4]      gt_boxes / M in fp32
+        gt_masks      fp32  [G, mh, mw] with use_mini_mask, [G, M, M] without; 0 / 1
+        areas         int32 [G]
+        bad           int32 [1]         instances without a pixel
+
+    Nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape or size or a non-contiguous tensor
+    ValueError, a CPU tensor NotImplementedError: there is no torch form."""
+    named = (('frame_u8', frame_u8), ('inst_map', inst_map), ('ids', ids))
+    _are_tensors(named)
+    if frame_u8.dtype != torch.uint8:
+        raise TypeError('frame_u8 must be %s, got %s' % (torch.uint8, frame_u8.dtype))
+    if frame_u8.dim() != 3 or frame_u8.shape[2] != 3:
+        raise ValueError('frame_u8 must be uint8 [H, W, 3], got %s' % (tuple(frame_u8.shape),))
+    H, W, _ = frame_u8.shape
+    if inst_map.dtype == torch.int32:
+        if tuple(inst_map.shape) != (H, W):
+            raise ValueError('an int32 inst_map must be [H, W] = %s, got %s' % ((H, W), tuple(inst_map.shape)))
+    elif inst_map.dtype == torch.uint8:
+        if tuple(inst_map.shape) != (H, W, 3):
+            raise ValueError('a uint8 inst_map must be [H, W, 3] = %s, got %s' % ((H, W, 3), tuple(inst_map.shape)))
+    else:
+        raise TypeError('inst_map must be %s [H, W] or %s [H, W, 3], got %s' % (torch.int32, torch.uint8, inst_map.dtype))
+    if ids.dtype != torch.int32:
+        raise TypeError('ids must be %s, got %s' % (torch.int32, ids.dtype))
+    if ids.dim() != 1:
+        raise ValueError('ids must be [G], got %s' % (tuple(ids.shape),))
+    G = ids.shape[0]
+    if G < 1 or G > TRAINING_ITEM_MAX_BOXES:
+        raise ValueError('G = %d; 1 to %d instances are supported' % (G, TRAINING_ITEM_MAX_BOXES))
+    plan_host = _training_item_plan(plan_host)
+    M = int(plan_host[4])
+    if M < 1 or M > TRAINING_ITEM_MAX_DIM:
+        raise ValueError('IMAGE_MAX_DIM %d; 1 to %d is supported' % (M, TRAINING_ITEM_MAX_DIM))
+    mini = bool(use_mini_mask)
+    mh, mw = (int(mini_shape[0]), int(mini_shape[1])) if mini else (M, M)
+    if mini and (mh < 1 or mw < 1 or mh > TRAINING_ITEM_MAX_MINI or mw > TRAINING_ITEM_MAX_MINI):
+        raise ValueError('mini-masks of %d x %d; each side 1 to %d is supported' % (mh, mw, TRAINING_ITEM_MAX_MINI))
+    _contiguous(named)
+    _on_one_device(named, 'the training item only runs on the GPU')
+    dev = frame_u8.device
+    with torch.cuda.device(dev):
+        plan = torch.from_numpy(plan_host).to(dev)   # the one upload
+        ws = torch.empty(training_item_workspace_bytes(1, H, W, G), dtype=torch.uint8, device=dev)
+        image = torch.empty(3, M, M, dtype=torch.float32, device=dev)
+        boxes_int = torch.empty(G, 4, dtype=torch.int32, device=dev)
+        boxes = torch.empty(G, 4, dtype=torch.float32, device=dev)
+        boxes_norm = torch.empty(G, 4, dtype=torch.float32, device=dev)
+        masks = torch.empty(G, mh, mw, dtype=torch.float32, device=dev)
+        areas = torch.empty(G, dtype=torch.int32, device=dev)
+        bad = torch.empty(1, dtype=torch.int32, device=dev)
+        check(lib().sdn_training_item(ptr(frame_u8), ptr(inst_map), int(inst_map.dtype == torch.uint8), ptr(ids), H, W, G,
+                                      plan_host.ctypes.data, ptr(plan), plan_host.size, int(mini), mh if mini else 0, mw if mini else 0,
+                                      ptr(ws), ws.numel(), ptr(image), ptr(boxes_int), ptr(boxes), ptr(boxes_norm), ptr(masks), ptr(areas),
+                                      ptr(bad), stream()))
+    return image, boxes_int, boxes, boxes_norm, masks, areas, bad
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -79,7 +79,8 @@ const char* sdn_last_error(void);
  * sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added; still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd,
  * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
  * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
- * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added -- new entry
+ * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added; still 20: sdn_training_item_workspace_bytes,
+ * sdn_training_item_image, sdn_training_item added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1171,6 +1172,38 @@ int sdn_rpn_targets_workspace_bytes(int A, int G, int T, size_t* out);
 int sdn_rpn_targets(const double* anchors, const void* gt_class_ids, const void* gt_boxes, const float* keys, int A, int G,
                     int ids_int64, int boxes_int32, const int32_t* gt_count, int T, const double* std_dev, int32_t* rpn_match,
                     float* rpn_bbox, int32_t* rows, int32_t* counts, void* workspace, size_t workspace_bytes, sdnStream stream);
+
+/* The training item of Mask R-CNN for one image (csrc/training_item.hip): what Dataset.__getitem__ (geometric/maskrcnn/model.py:1371-1409)
+ * makes on the host through load_image_gt (:1154-1211) -- utils.resize_image (utils.py:272-320: scipy.misc.imresize of a uint8 RGB
+ * frame = Pillow's BILINEAR resize), resize_mask (:323-335: ndimage.zoom(order=0) and np.pad), np.fliplr (model.py:1189-1190),
+ * extract_bboxes (utils.py:26-49), minimize_mask (:338-353) and mold_image (model.py:2196-2201) -- and the division of the boxes by the
+ * image shape (:1790-1794).  sdn_training_item_image is its image half alone, for B frames of one size: mold_inputs (:2046-2082).
+ * All pointers but plan_host are DEVICE memory.  frames uint8 [B, H, W, 3]; plan_host / plan: the parameter block (csrc/
+ * training_item_check.h: TriPlan, 24 ints, then the tables it names by offset: Pillow's bounds and fixed-point coefficients W -> ow and
+ * H -> oh, absent for a pass Pillow skips; the source row of every resized row and the source column of every resized column of
+ * ndimage.zoom, -1 where it yields the constant 0; fp32(fp64(byte) - MEAN_PIXEL[c]) as a [3][256] table) in HOST memory, read and
+ * checked during the call, and its copy on the device, n_plan ints each.  inst_map int32 [H, W] (map_rgb 0) or uint8 [H, W, 3]
+ * (map_rgb 1: the id of a pixel is r << 16 | g << 8 | b); ids int32 [G], 1 <= G <= 128: instance g is inst_map == ids[g].
+ * The colour jitter of the plan is applied to the frame's pixels before the resize; the horizontal pass is rounded to bytes, then the
+ * vertical pass; the zero padding comes first and the padded image and masks are mirrored then (flip).  Results: image fp32
+ * [B, 3, M, M]; gt_boxes_int int32 [G, 4] = (y1, x1, y2, x2), first and last + 1 row and column of the instance in the padded,
+ * mirrored frame, zeros for an instance without a pixel; gt_boxes the same as fp32; gt_boxes_norm = gt_boxes / M in fp32; areas int32
+ * [G]: the instance's pixels; bad int32 [1]: the instances without a pixel (minimize_mask raises there); gt_masks fp32 0 / 1:
+ * [G, mini_h, mini_w] with use_mini_mask -- bytescale of the crop (0 / 255; all 0 for a crop whose every pixel is set, where
+ * cmax == cmin), Pillow's BILINEAR resize of the crop with the coefficients computed on the device in fp64 (precompute_coeffs,
+ * normalize_coeffs_8bpc) and >= 128; all zero for an instance without a pixel -- or [G, M, M] without: the mask itself.
+ * M <= 1024, W <= 4096, mini_h and mini_w <= 56, H W <= 2^21 with a contrast op.  Every element is written: nothing needs clearing.
+ * Launches on `stream`: one more with a contrast op (the frame's luma mean), the image, then for the item the boxes and the masks.
+ * Integer atomics only: two calls on the same inputs give the same bits.  Nothing is copied to the host.  Workspace: query first
+ * (G = 0 for the image alone); 16-byte aligned.  SDN_EINVAL with a message, before any launch, for sizes outside these ranges, a
+ * plan that does not fit them or the frame, NULL or misaligned pointers and a workspace that is too small. */
+int sdn_training_item_workspace_bytes(int B, int H, int W, int G, size_t* out);
+int sdn_training_item_image(const uint8_t* frames, int B, int H, int W, const int32_t* plan_host, const int32_t* plan, long n_plan,
+                            void* workspace, size_t workspace_bytes, float* image, sdnStream stream);
+int sdn_training_item(const uint8_t* frame, const void* inst_map, int map_rgb, const int32_t* ids, int H, int W, int G,
+                      const int32_t* plan_host, const int32_t* plan, long n_plan, int use_mini_mask, int mini_h, int mini_w,
+                      void* workspace, size_t workspace_bytes, float* image, int32_t* gt_boxes_int, float* gt_boxes,
+                      float* gt_boxes_norm, float* gt_masks, int32_t* areas, int32_t* bad, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
