@@ -62,6 +62,13 @@ __device__ __forceinline__ void prop_prefix(const int32_t* head, int A, int K, i
     *rank = (int)r;
 }
 
+// Zeroes the histograms and the cursor.  A kernel, not hipMemsetAsync: the call is then a plain chain of kernel launches, which a
+// captured graph replays in order (a replay that left the head of the previous replay in place selected fewer than K keys).
+__global__ __launch_bounds__(PROP_THREADS) void k_prop_clear(int32_t* __restrict__ head)
+{
+    for (int i = threadIdx.x; i < PROP_HEAD_INTS; i += PROP_THREADS) head[i] = 0;
+}
+
 __global__ __launch_bounds__(PROP_THREADS) void k_prop_hist(const PropSelect S, const int pass)
 {
     __shared__ int h[256];
@@ -179,6 +186,7 @@ struct PropDecode {
     const uint64_t* keys;    // [K] unsorted
     const float* deltas;     // [A, 4]
     const float* anchors;    // [A, 4]
+    uint32_t A;
     float std_dev[4];
     float height, width;
     int K, N;                // N: the sorting network's size, a power of two >= K
@@ -195,7 +203,8 @@ __global__ __launch_bounds__(PROP_SORT_THREADS) void k_prop_sort(const PropDecod
     __syncthreads();
     prop_sort_keys(s, D.N, tid, PROP_SORT_THREADS);
     for (int r = tid; r < D.K; r += PROP_SORT_THREADS) {
-        const uint32_t idx = prop_key_index(s[r]);
+        uint32_t idx = prop_key_index(s[r]);
+        if (idx >= D.A) idx = D.A - 1u;   // every selected key names an anchor; the bound only keeps a broken key inside the buffers
         D.order[r] = (int32_t)idx;
         const float* a = D.anchors + 4 * (size_t)idx;
         const float* d = D.deltas + 4 * (size_t)idx;
@@ -281,7 +290,7 @@ SDN_API int sdn_proposal_layer(const float* rpn_probs, const float* rpn_bbox, co
     S.keys = (uint64_t*)(ws + L.keys);
     float* areas = (float*)(ws + L.areas);
     unsigned long long* mask = (unsigned long long*)(ws + L.mask);
-    if (hipMemsetAsync(S.head, 0, sizeof(int32_t) * PROP_HEAD_INTS, st) != hipSuccess) return fail(SDN_ELAUNCH, "sdn_proposal_layer: memset");
+    hipLaunchKernelGGL(k_prop_clear, dim3(1), dim3(PROP_THREADS), 0, st, S.head);
     const unsigned chunks = (unsigned)prop_chunks(A);
     for (int pass = 0; pass < 4; pass++) hipLaunchKernelGGL(k_prop_hist, dim3(chunks), dim3(PROP_THREADS), 0, st, S, pass);
     hipLaunchKernelGGL(k_prop_ties, dim3(chunks), dim3(PROP_THREADS), 0, st, S);
@@ -291,6 +300,7 @@ SDN_API int sdn_proposal_layer(const float* rpn_probs, const float* rpn_bbox, co
     D.keys = S.keys;
     D.deltas = rpn_bbox;
     D.anchors = anchors;
+    D.A = (uint32_t)A;
     for (int k = 0; k < 4; k++) D.std_dev[k] = std_dev[k];
     D.height = (float)height;
     D.width = (float)width;

@@ -2298,6 +2298,102 @@ def training_item(frame_u8, inst_map, ids, plan_host, use_mini_mask, mini_shape)
     return image, boxes_int, boxes, boxes_norm, masks, areas, bad
 
 
+RPN_OUTPUTS_MAX_LEVELS, RPN_OUTPUTS_MAX_K, RPN_OUTPUTS_TILE = 8, 16, 64   # csrc/rpn_outputs_check.h: RPO_MAX_LEVELS, RPO_MAX_K, RPO_TILE
+RPN_OUTPUTS_MAX_BATCH = 65535                                             # RPO_MAX_BATCH
+
+
+def _rpo_ints(values):
+    return (ctypes.c_int * len(values))(*[int(v) for v in values])
+
+
+def _rpo_ptrs(tensors):
+    return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
+
+
+class RpnOutputsFn(torch.autograd.Function):
+    """The tail of RPN.forward on every pyramid level and the three cats of MaskRCNN.predict (geometric/maskrcnn/model.py:896-911,
+    :1729-1740) -- sdn_rpn_outputs_fwd / _bwd (include/sdn_hip.h), one launch each way.  Inputs: the L class maps, then the L box maps.
+    Returns (rpn_class_logits [B, A, 2], rpn_probs [B, A, 2], rpn_bbox [B, A, 4]).  An output that nothing differentiates arrives in
+    backward as None and is not read: no buffer of zeros is made for it.  `rpn_outputs` below checks types and shapes."""
+
+    @staticmethod
+    def forward(ctx, *maps):
+        L = len(maps) // 2
+        cls, box = maps[:L], maps[L:]
+        B, k = cls[0].shape[0], cls[0].shape[1] // 2
+        H, W = [m.shape[2] for m in cls], [m.shape[3] for m in cls]
+        A = k * sum(h * w for h, w in zip(H, W))
+        dev = cls[0].device
+        with torch.cuda.device(dev):
+            logits = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
+            probs = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
+            bbox = torch.empty(B, A, 4, dtype=torch.float32, device=dev)
+            check(lib().sdn_rpn_outputs_fwd(_rpo_ptrs(cls), _rpo_ptrs(box), _rpo_ints(H), _rpo_ints(W), L, k, B, ptr(logits), ptr(probs),
+                                            ptr(bbox), stream()))
+        ctx.save_for_backward(probs)
+        ctx.sizes = (L, k, B, H, W)
+        ctx.set_materialize_grads(False)
+        return logits, probs, bbox
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_logits, g_probs, g_bbox):
+        L, k, B, H, W = ctx.sizes
+        if not any(ctx.needs_input_grad):
+            return (None,) * (2 * L)
+        (probs,) = ctx.saved_tensors
+        dev = probs.device
+        with torch.cuda.device(dev):
+            g_logits, g_probs, g_bbox = [None if g is None else g.to(torch.float32).contiguous() for g in (g_logits, g_probs, g_bbox)]
+            g_cls = [torch.empty(B, 2 * k, h, w, dtype=torch.float32, device=dev) for h, w in zip(H, W)]
+            g_box = [torch.empty(B, 4 * k, h, w, dtype=torch.float32, device=dev) for h, w in zip(H, W)]
+            check(lib().sdn_rpn_outputs_bwd(ptr(g_logits), ptr(g_probs), ptr(g_bbox), ptr(probs), _rpo_ints(H), _rpo_ints(W), L, k, B,
+                                            _rpo_ptrs(g_cls), _rpo_ptrs(g_box), stream()))
+        return tuple(g if need else None for g, need in zip(g_cls + g_box, ctx.needs_input_grad))
+
+
+def rpn_outputs(class_maps, bbox_maps):
+    """(rpn_class_logits fp32 [B, A, 2], rpn_probs fp32 [B, A, 2], rpn_bbox fp32 [B, A, 4]) from the outputs of conv_class and conv_bbox
+    on the L pyramid levels (1 <= L <= 8): class_maps[l] fp32 [B, 2k, H_l, W_l], bbox_maps[l] fp32 [B, 4k, H_l, W_l], contiguous CUDA
+    tensors, k anchors per location (1 <= k <= 16), A = k * sum H_l W_l.  It is what RPN.forward does after its convs
+    (geometric/maskrcnn/model.py:896-911) and the cat over the levels of :1739: level l starts at anchor k * sum_{m<l} H_m W_m, anchor
+    (y * W + x) * k + a, component j, is channel a * 2 + j (boxes: a * 4 + j) at pixel (y, x).  Logits and boxes are copies bit for
+    bit, rpn_probs the fp32 softmax over (bg, fg).  One launch forward, one backward; differentiable in all 2L maps, the same bits
+    every run; nothing is copied to the host.  A wrong type or dtype raises TypeError, a wrong shape or size or a non-contiguous tensor
+    ValueError, a CPU tensor NotImplementedError: there is no torch form."""
+    try:
+        cls, box = list(class_maps), list(bbox_maps)
+    except TypeError:
+        raise TypeError('class_maps and bbox_maps must be sequences of tensors')
+    if not 1 <= len(cls) <= RPN_OUTPUTS_MAX_LEVELS or len(box) != len(cls):
+        raise ValueError('%d class maps and %d box maps; 1 to %d levels with one of each are supported' % (len(cls), len(box),
+                                                                                                            RPN_OUTPUTS_MAX_LEVELS))
+    named = [('class_maps[%d]' % l, m) for l, m in enumerate(cls)] + [('bbox_maps[%d]' % l, m) for l, m in enumerate(box)]
+    _are_tensors(named)
+    for name, m in named:
+        if m.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, m.dtype))
+        if m.dim() != 4 or min(m.shape) < 1:
+            raise ValueError('%s must be fp32 [B, channels, H, W] without an empty axis, got %s' % (name, tuple(m.shape)))
+    B, c2 = cls[0].shape[0], cls[0].shape[1]
+    k = c2 // 2
+    if c2 % 2 or not 1 <= k <= RPN_OUTPUTS_MAX_K:
+        raise ValueError('class_maps[0] has %d channels; 2k with k = 1 to %d anchors per location are supported' % (c2, RPN_OUTPUTS_MAX_K))
+    if B > RPN_OUTPUTS_MAX_BATCH:
+        raise ValueError('batch %d; 1 to %d are supported' % (B, RPN_OUTPUTS_MAX_BATCH))
+    for l, (c, b) in enumerate(zip(cls, box)):
+        if tuple(c.shape) != (B, 2 * k, c.shape[2], c.shape[3]):
+            raise ValueError('class_maps[%d] must be [%d, %d, H, W], got %s' % (l, B, 2 * k, tuple(c.shape)))
+        if tuple(b.shape) != (B, 4 * k, c.shape[2], c.shape[3]):
+            raise ValueError('bbox_maps[%d] must be [%d, %d, %d, %d], got %s' % (l, B, 4 * k, c.shape[2], c.shape[3], tuple(b.shape)))
+    A = k * sum(c.shape[2] * c.shape[3] for c in cls)
+    if B * A * 4 >= 2 ** 31:
+        raise ValueError('B * A * 4 = %d must stay below 2^31' % (B * A * 4))
+    _contiguous(named)
+    _on_one_device(named, 'the RPN output kernels only run on the GPU')
+    return RpnOutputsFn.apply(*(cls + box))
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

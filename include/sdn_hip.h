@@ -80,7 +80,7 @@ const char* sdn_last_error(void);
  * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
  * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
  * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added; still 20: sdn_training_item_workspace_bytes,
- * sdn_training_item_image, sdn_training_item added -- new entry
+ * sdn_training_item_image, sdn_training_item added; still 20: sdn_rpn_outputs_fwd, sdn_rpn_outputs_bwd added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1204,6 +1204,28 @@ int sdn_training_item(const uint8_t* frame, const void* inst_map, int map_rgb, c
                       const int32_t* plan_host, const int32_t* plan, long n_plan, int use_mini_mask, int mini_h, int mini_w,
                       void* workspace, size_t workspace_bytes, float* image, int32_t* gt_boxes_int, float* gt_boxes,
                       float* gt_boxes_norm, float* gt_masks, int32_t* areas, int32_t* bad, sdnStream stream);
+
+/* The RPN's outputs over all pyramid levels (csrc/rpn_outputs.hip): what RPN.forward does after its convs on every level,
+ * geometric/maskrcnn/model.py:896-911 -- permute(0, 2, 3, 1).contiguous().view of the class map (:897-899) and of the box map
+ * (:909-911), the softmax over (bg, fg) (:902) -- and the three torch.cat(dim=1) over the levels in MaskRCNN.predict (:1729-1740).
+ * class_maps / bbox_maps: L pointers in host memory (1 <= L <= 8), level l fp32 [B, 2k, H[l], W[l]] / [B, 4k, H[l], W[l]] contiguous
+ * NCHW on the device, as conv_class / conv_bbox emit them; k anchors per location (1 <= k <= 16), B images (1 <= B <= 65535).  With
+ * A = k * sum_l H[l] W[l]: rpn_class_logits fp32 [B, A, 2], rpn_probs fp32 [B, A, 2], rpn_bbox fp32 [B, A, 4].  Level l starts at
+ * anchor k * sum_{m<l} H[m] W[m]; in a level, anchor (y * W + x) * k + a, component j, is channel a * 2 + j (boxes: a * 4 + j) at pixel
+ * (y, x).  Logits and boxes are copies, bit for bit; rpn_probs is exp(x_j - max(x_0, x_1)) / (e_0 + e_1) in fp32, a non-finite logit
+ * following the formula ((+inf, x), (-inf, -inf) and a NaN give NaN twice, as torch's softmax).
+ * _fwd, ONE launch: every output element is written once; no memset, no atomics, no workspace.  The maps need 4-byte alignment only
+ * (views into a larger buffer are fine), the three outputs 16 bytes.
+ * _bwd, ONE launch: grad_logits, grad_probs, grad_bbox (shapes of the outputs; each may be NULL and then counts as zero without being
+ * read) and the saved rpn_probs (read only beside grad_probs) -> grad_class_maps / grad_bbox_maps, L pointers each, every element of
+ * the 2L gradients written once: the boxes' is the transposed copy, the classes' g_logit_j + p_j * (g_p_j - (g_p_0 p_0 + g_p_1 p_1)),
+ * which without grad_probs is the transposed copy of grad_logits.  The same bits every run.
+ * SDN_EINVAL with a message, before any launch, for L, k or B outside these ranges, a level with H or W < 1, B * A * 4 not below 2^31,
+ * NULL pointers (but the three gradients) and misaligned ones.  Nothing is copied to the host. */
+int sdn_rpn_outputs_fwd(const float* const* class_maps, const float* const* bbox_maps, const int* H, const int* W, int L, int k, int B,
+                        float* rpn_class_logits, float* rpn_probs, float* rpn_bbox, sdnStream stream);
+int sdn_rpn_outputs_bwd(const float* grad_logits, const float* grad_probs, const float* grad_bbox, const float* rpn_probs, const int* H,
+                        const int* W, int L, int k, int B, float* const* grad_class_maps, float* const* grad_bbox_maps, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
