@@ -17,7 +17,7 @@
 //   Every partial sum has a fixed order, so the result is deterministic run to run (the reference's is too);
 //   it differs from the reference's strictly serial sum by float re-association only (~1e-7 relative).
 //   Faces whose chunks do not fit the workspace fall back to the literal serial walk inside k_edge_reduce.
-//   Silhouette fast path (only alpha is differentiated): k_hmap + k_compact_rows build the rows' non-zero lists,
+//   Silhouette fast path (only alpha is differentiated): k_cover_bits + k_compact_rows build the rows' non-zero lists,
 //     k_edge_scan_sil (64 edge pixels per wave) files every "out" scan under its row, k_edge_rows evaluates a row's
 //     scans from LDS, k_chunk_sum adds them to their chunks and k_edge_reduce runs as above.
 //   Frame step (that path with a vertex sink: sdn_render_maps_bwd differentiating the silhouette alone):
@@ -65,11 +65,10 @@ struct BwdParams {
     uint32_t* counter;      // [2] chunks allocated so far; faces on the serial-fallback list
     uint4* chunk_desc;      // [cap] {global face, edge*2+axis, d0_start, count}
     float2* chunk_out;      // [cap]
-    const float* hmap;      // [bs,S,S]  silhouette-only fast path: max(-g_alpha, 0) on background pixels, else 0
-    const float* hmapT;     // [bs,S,S]  the same, transposed (column scans become coalesced)
-    // sparse form of hmap / hmapT rows (k_compact_rows): h is zero on every covered pixel and wherever the upstream
-    // gradient is >= 0, and K5's "out" scans run from an edge all the way to the image border, so most of what they
-    // read is zero.  row r = (b * S + line) of the row-major map, rows [bs*S, 2*bs*S) the transposed one.
+    // silhouette-only fast path: h = max(-g_alpha, 0) on background pixels, else 0, in sparse form (k_compact_rows): h is zero
+    // on every covered pixel and wherever the upstream gradient is >= 0, and K5's "out" scans run from an edge all the way to
+    // the image border, so most of what they would read is zero.  row r = (b * S + y) is an image row, rows [bs*S, 2*bs*S)
+    // are the image columns (b * S + x).
     const uint16_t* nz_cnt;  // [2*bs*S, S+1]  number of non-zeros in [0, x)
     const uint16_t* nz_pos;  // [2*bs*S, S]    their positions, ascending
     const float* nz_val;     // [2*bs*S, S]    their values
@@ -220,13 +219,12 @@ __device__ __forceinline__ void edge_pixel(const BwdParams& P, const MapReader& 
     }
     const bool nz1 = w.p[1][0] != fd0, nz0 = w.p[0][0] != fd0;
     const float den1 = w.p[1][0] - fd0, den0 = fd0 - w.p[0][0];
-    const float* hline = nullptr;
-    if (P.hmap && use_alpha && !use_rgb) hline = (axis == 0 ? P.hmapT : P.hmap) + ((size_t)M.b * S + d0) * S;
+    const bool sparse_rows = P.nz_cnt && use_alpha && !use_rgb;
 
     // "out" pass (rasterize.py:600-656): from the pixel just outside the edge to the image border
-    if (f_in == fn && hline) {
+    if (f_in == fn && sparse_rows) {
         // silhouette-only: alpha_in = 1, so diff_grad = (alpha(p) - 1) * g(p) is positive only on background pixels
-        // with g < 0, where it equals -g: exactly what k_hmap stored (0 elsewhere).  Only the non-zero entries of the
+        // with g < 0, where it equals -g: exactly the h of k_compact_rows (0 elsewhere).  Only the non-zero entries of the
         // segment are visited (coalesced reads of the row's compact list); the skipped terms are exactly the ones the
         // reference drops with `if (diff_grad <= 0) continue` (rasterize.py:644,715).
         const int d1_limit = (0 < w.direction) ? S - 1 : 0;
@@ -298,103 +296,156 @@ __global__ __launch_bounds__(256) void k_mark_visible(const int32_t* __restrict_
     if (fn >= 0) visible[(i / ((long)S * S)) * nf + fn] = 1u;
 }
 
-// h(x,y) = max(-g_alpha(x,y), 0) on background pixels, 0 on covered ones; written TRANSPOSED only (r06: the image rows are formed
-// by k_compact_rows itself from the face-index map -- the row-major h map was 38 MB written and read back per frame)
-// (the same pass over the face-index map sets the visible flags k_mark_visible would: one launch less in the silhouette path)
-__global__ __launch_bounds__(256) void k_hmap(const BwdParams P, float* __restrict__ hmapT)
+// Silhouette set-up, pass 1: ONE pass over the face-index map, a 32 x 32 tile of internal pixels per workgroup.  It sets the visible
+// flags k_mark_visible would and writes one coverage bit per pixel (set = covered), twice: cov[b][y][x / 32] for the image rows and
+// covT[b][x][y / 32] for the image columns (rows of cdiv(S, 32) words; bits past S are clear).  The same grid transposes the upstream
+// gradient at OUTPUT resolution, gT[b][xo][yo] = g_alpha_out[b][yo][xo], so a column's values lie side by side as a row's do.
+// (Before the bit maps this pass formed h = max(-g, 0) and stored it as a dense transposed fp32 map of the internal size, 38 MB per frame
+// written here and read back by k_compact_rows, which also read the 38 MB face-index map a second time for the image rows: all of
+// it to carry one bit per pixel.  profiles/sil_setup_bits.md)
+__global__ __launch_bounds__(256) void k_cover_bits(const BwdParams P, uint32_t* __restrict__ cov, uint32_t* __restrict__ covT,
+                                                    float* __restrict__ gT)
 {
-    __shared__ float tile[32][33];
-    const int S = P.S, b = blockIdx.z;
-    const MapReader M(P, b);
-    const int x = blockIdx.x * 32 + (threadIdx.x & 31);
+    __shared__ uint32_t flag[32][33];
+    __shared__ float gt[32][33];
+    const int S = P.S, b = blockIdx.z, W = (S + 31) >> 5;
+    const bool aa = (P.flags & SDN_AA) != 0;
+    const int R = aa ? S / 2 : S, n = aa ? 16 : 32;   // the tile's share of the output image: n x n values
+    const int lx = threadIdx.x & 31, l8 = threadIdx.x >> 5;
+    const unsigned half = threadIdx.x & 32;   // a wave holds two tile rows: lanes 0-31 the even one, 32-63 the odd one
+    const int x = blockIdx.x * 32 + lx;
+    // all eight loads of a thread first: the stores below may alias the maps as far as the compiler knows
+    int fn[4];
+    float gv[4];
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const int ly = (threadIdx.x >> 5) + 8 * r, y = blockIdx.y * 32 + ly;
-        float h = 0.0f;
-        if (x < S && y < S) {
-            const int fn = M.fidx(x, y);
-            if (fn < 0) {
-                const float t = (0.0f - 1.0f) * M.g_alpha(x, y);
-                h = t > 0.0f ? t : 0.0f;
-            } else {
-                P.visible[(size_t)b * P.nf + fn] = 1u;
-            }
-        }
-        tile[ly][threadIdx.x & 31] = h;
+        const int ly = l8 + 8 * r, y = blockIdx.y * 32 + ly;
+        const int xo = blockIdx.x * n + lx, yo = blockIdx.y * n + ly;
+        fn[r] = (x < S && y < S) ? P.face_index_map[((size_t)b * S + y) * S + x] : -1;
+        gv[r] = (lx < n && ly < n && xo < R && yo < R) ? P.g_alpha_out[((size_t)b * R + yo) * R + xo] : 0.0f;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int ly = l8 + 8 * r, y = blockIdx.y * 32 + ly;
+        const bool covered = fn[r] >= 0;
+        // a face's pixels lie side by side: only the first lane of a run of equal face numbers stores the flag
+        const int left = __shfl_up(fn[r], 1);
+        if (covered && ((threadIdx.x & 63) == 0 || left != fn[r])) P.visible[(size_t)b * P.nf + fn[r]] = 1u;
+        flag[ly][lx] = covered ? 1u : 0u;
+        gt[ly][lx] = gv[r];
+        const unsigned long long m = __ballot(covered);
+        if (lx == 0 && y < S) cov[((size_t)b * S + y) * W + blockIdx.x] = (uint32_t)(m >> half);
     }
     __syncthreads();
-    const int yt = blockIdx.y * 32 + (threadIdx.x & 31);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
-        const int lx = (threadIdx.x >> 5) + 8 * r, xt = blockIdx.x * 32 + lx;
-        if (xt < S && yt < S) hmapT[((size_t)b * S + xt) * S + yt] = tile[threadIdx.x & 31][lx];
+        const int lc = l8 + 8 * r, xt = blockIdx.x * 32 + lc;   // tile column lc; lx is the tile row now
+        const unsigned long long m = __ballot(flag[lx][lc] != 0u);
+        if (lx == 0 && xt < S) covT[((size_t)b * S + xt) * W + blockIdx.y] = (uint32_t)(m >> half);
+        const int xo = blockIdx.x * n + lc, yo = blockIdx.y * n + lx;
+        if (lx < n && lc < n && xo < R && yo < R) gT[((size_t)b * R + xo) * R + yo] = gt[lx][lc];
     }
 }
 
-// One WAVE per map row: prefix counts of the non-zero entries and their compact (position, value) list.
-// (rows [0, rows_per_map) come from `maps`, the next rows_per_map from `mapsT`: both orientations in one launch)
-// r06: was one 256-thread workgroup per row with four barriers per 256 positions (the wave totals met in LDS); a wave carries the
-// running count in a register and needs neither LDS nor barriers: 34 -> 2x us.  Two positions per lane and round (8-byte loads).
-__global__ __launch_bounds__(256) void k_compact_rows(const BwdParams P, const float* __restrict__ mapsT,
+// Silhouette set-up, pass 2.  One WAVE per map row (rows [0, rows_per_map) are image rows, the next rows_per_map image columns):
+// prefix counts of the non-zero entries of h and their compact (position, value) list, where
+//   h = max(-g_alpha, 0) on background pixels, 0 on covered ones
+// is formed on the fly from the row's coverage words and its line of the upstream gradient.  Position d of image row y takes
+// g_alpha_out[R-1 - (y >> sh)][d >> sh], position d of image column x takes gT[x >> sh][R-1 - (d >> sh)] (MapReader::oidx: vertical
+// flip, 2 x 2 expansion with sh = 1 under anti-aliasing): consecutive floats either way, descending for a column.
+// A lane takes output element e = lane + 64 j of a group of 64 * CR; all CR gradient loads and coverage words of the group are in
+// flight before the first ballot (it was six dependent load -> ballot -> store rounds of 128 positions).  The running count
+// stays in a register: no LDS, no barriers.
+constexpr int CR = 6;   // elements per lane and group: 384 output elements, a whole row of the 768-pixel frame step
+template <bool AA>
+__global__ __launch_bounds__(256) void k_compact_rows(const BwdParams P, const uint32_t* __restrict__ cov,
+                                                      const uint32_t* __restrict__ covT, const float* __restrict__ gT,
                                                       size_t rows_per_map, int S, uint16_t* __restrict__ cnt,
                                                       uint16_t* __restrict__ pos, float* __restrict__ val)
 {
     const int lane = threadIdx.x & 63;
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= 2 * rows_per_map) return;   // (wave-uniform)
-    const bool image_row = row < rows_per_map;   // h from the face-index map and the upstream gradient (k_hmap's expression)
-    const float* src = mapsT + (image_row ? 0 : row - rows_per_map) * S;
-    const int yb = (int)(row / (size_t)S), yy = (int)(row % (size_t)S);
-    const MapReader M(P, image_row ? yb : 0);
-    auto h_at = [&](const int x) {
-        float h = 0.0f;
-        if (M.fidx(x, yy) < 0) {
-            const float t = (0.0f - 1.0f) * M.g_alpha(x, yy);
-            h = t > 0.0f ? t : 0.0f;
-        }
-        return h;
-    };
+    const bool image_row = row < rows_per_map;
+    const size_t line = image_row ? row : row - rows_per_map;   // b * S + y, or b * S + x
+    const int b = (int)(line / (size_t)S), d0 = (int)(line % (size_t)S);
+    const int R = AA ? S / 2 : S, W = (S + 31) >> 5;
+    const uint32_t* cw = (image_row ? cov : covT) + line * W;
+    // the line's R gradient values: element e of an image row is gl[e], of an image column gl[R-1 - e]
+    const float* gl = image_row ? P.g_alpha_out + ((size_t)b * R + (R - 1 - (AA ? d0 >> 1 : d0))) * R
+                                : gT + ((size_t)b * R + (AA ? d0 >> 1 : d0)) * R;
     uint16_t* c = cnt + row * (S + 1);
+    // rows start at 2-byte alignment: under AA a lane stores its two counts as one aligned 32-bit word, (c[2e], c[2e+1]) in a row
+    // that starts on a word and (c[2e+1], c[2e+2]) in one that does not (c[2e+2] is the count behind the lane's own two positions)
+    const bool odd = ((row * (size_t)(S + 1)) & 1) != 0;
+    const unsigned long long below = (1ull << lane) - 1ull;
     int base = 0;
-    for (int x0 = 0; x0 < S; x0 += 128) {
-        const int x = x0 + 2 * lane;
-        float h0 = 0.0f, h1 = 0.0f;
-        if (image_row) {
-            if (x < S) h0 = h_at(x);
-            if (x + 1 < S) h1 = h_at(x + 1);
-        } else if (x + 1 < S && ((S & 1) == 0)) {   // (rows of an even S are 8-byte aligned)
-            const float2 v = *reinterpret_cast<const float2*>(src + x);
-            h0 = v.x;
-            h1 = v.y;
-        } else {
-            if (x < S) h0 = src[x];
-            if (x + 1 < S) h1 = src[x + 1];
-        }
-        const bool nz0 = h0 > 0.0f, nz1 = h1 > 0.0f;
-        const unsigned long long m0 = __ballot(nz0), m1 = __ballot(nz1);
-        const unsigned long long below = (1ull << lane) - 1ull;
-        // entries in position order: lane l's two positions come after both positions of every lane below it
-        const int i0 = base + __popcll(m0 & below) + __popcll(m1 & below);
-        const int i1 = i0 + (nz0 ? 1 : 0);
-        if (x < S) {
-            c[x] = (uint16_t)i0;
-            if (nz0) {
-                pos[row * S + i0] = (uint16_t)x;
-                val[row * S + i0] = h0;
+    if (AA && odd && lane == 0) c[0] = 0;
+    for (int e0 = 0; e0 < R; e0 += 64 * CR) {
+        float g[CR];
+        uint32_t w[CR];
+#pragma unroll
+        for (int j = 0; j < CR; j++) {
+            const int e = e0 + 64 * j + lane;
+            g[j] = 0.0f;
+            w[j] = 0u;
+            if (e < R) {
+                g[j] = gl[image_row ? e : R - 1 - e];
+                w[j] = cw[AA ? e >> 4 : e >> 5];
             }
         }
-        if (x + 1 < S) {
-            c[x + 1] = (uint16_t)i1;
-            if (nz1) {
-                pos[row * S + i1] = (uint16_t)(x + 1);
-                val[row * S + i1] = h1;
+#pragma unroll
+        for (int j = 0; j < CR; j++) {
+            const int e = e0 + 64 * j + lane;
+            if (e0 + 64 * j >= R) break;   // (wave-uniform)
+            const float t = (0.0f - 1.0f) * (AA ? g[j] * 0.25f : g[j]);
+            const float h = t > 0.0f ? t : 0.0f;
+            const bool in = e < R && h > 0.0f;
+            if (AA) {
+                const uint32_t two = w[j] >> (2 * (e & 15));
+                const bool nz0 = in && !(two & 1u), nz1 = in && !(two & 2u);
+                const unsigned long long m0 = __ballot(nz0), m1 = __ballot(nz1);
+                // entries in position order: lane l's two positions come after both positions of every lane below it
+                const int i0 = base + __popcll(m0 & below) + __popcll(m1 & below);
+                const int i1 = i0 + (nz0 ? 1 : 0), i2 = i1 + (nz1 ? 1 : 0);
+                if (e < R) {
+                    const int x = 2 * e;
+                    if (odd)
+                        *reinterpret_cast<uint32_t*>(c + x + 1) = (uint32_t)i1 | (uint32_t)i2 << 16;
+                    else
+                        *reinterpret_cast<uint32_t*>(c + x) = (uint32_t)i0 | (uint32_t)i1 << 16;
+                    if (nz0) {
+                        pos[row * S + i0] = (uint16_t)x;
+                        val[row * S + i0] = h;
+                    }
+                    if (nz1) {
+                        pos[row * S + i1] = (uint16_t)(x + 1);
+                        val[row * S + i1] = h;
+                    }
+                }
+                base += __popcll(m0) + __popcll(m1);
+            } else {
+                const bool nz = in && !((w[j] >> (e & 31)) & 1u);
+                const unsigned long long m = __ballot(nz);
+                const int i0 = base + __popcll(m & below);
+                if (e < R) {
+                    c[e] = (uint16_t)i0;
+                    if (nz) {
+                        pos[row * S + i0] = (uint16_t)e;
+                        val[row * S + i0] = h;
+                    }
+                }
+                base += __popcll(m);
             }
         }
-        base += __popcll(m0) + __popcll(m1);
     }
-    if (lane == 0) c[S] = (uint16_t)base;
+    if (lane == 0 && !(AA && odd)) c[S] = (uint16_t)base;
 }
 
+// (Measured and dropped with the bit maps, profiles/sil_setup_bits.md: tiles of 64 x 32 pixels in k_cover_bits, a wave per 256-byte row
+// piece, sixteen loads per thread, the column words built from the rows' ballots parked in LDS -- 17.5 .. 18.1 us against 17.8 .. 17.9;
+// alpha_out of k_edge_scan_sil as a bit test in cov instead of a load from the face-index map -- the scan kernel + 5 us: the
+// face-index line of the pixel outside the edge is mostly the one f_in fetched, the bit map's is a second line.)
 // (Measured and dropped, r05: k_hmap + k_compact_rows as ONE pass over the face-index map without the dense h maps -- nothing but
 // k_compact_rows reads them.  Image rows are easy (h on the fly, the same compaction); image COLUMNS were taken as bands of 32
 // columns, a 256-row chunk parked transposed in LDS, 32 rows of a column per thread (rotated LDS reads, counts written out
@@ -1201,12 +1252,13 @@ static void bwd_layout(int bs, int nf, int S, size_t off[14], uint32_t& cap, siz
     off[2] = off[10] + align256((size_t)4 * bs * S * sizeof(uint32_t));  // chunk_base i32[n]
     off[3] = off[2] + align256(n * sizeof(int32_t));    // chunk_desc uint4[cap]
     off[4] = off[3] + align256((size_t)cap * sizeof(uint4));  // chunk_out float2[cap]
-    off[5] = off[4] + align256((size_t)cap * sizeof(float2));          // (hmap: nothing stored)
-    off[6] = off[5];   // hmapT float[bs*S*S]  (r06: the row-major h map is gone; off[5] only names the fast path's flag pointer)
+    off[5] = off[4] + align256((size_t)cap * sizeof(float2));          // (unused)
+    off[6] = off[5];   // cov, covT u32[bs*S*cdiv(S,32)] each, in the slot of the dense h map of r06 (the sizes are part of the ABI)
     off[7] = off[6] + align256((size_t)bs * S * S * sizeof(float));                 // nz_cnt u16[2*bs*S*(S+1)]
     off[8] = off[7] + align256((size_t)2 * bs * S * (S + 1) * sizeof(uint16_t));    // nz_pos u16[2*bs*S*S]
     off[9] = off[8] + align256((size_t)2 * bs * S * S * sizeof(uint16_t));          // nz_val f32[2*bs*S*S]
     off[11] = off[9] + align256((size_t)2 * bs * S * S * sizeof(float));            // own_rec OwnerRec[2*bs*S * 3*S]
+                                                                                    // (its head: gT until k_edge_scan_sil runs)
     off[12] = off[11] + align256((size_t)2 * bs * S * 3 * S * sizeof(OwnerRec));  // own_out float2[cap*8]
     off[13] = off[12] + align256((size_t)cap * 8 * sizeof(float2));         // chunk_mask u8[cap]
     total = off[13] + align256((size_t)cap);
@@ -1278,8 +1330,6 @@ int sdn::rasterize_bwd_core(const VertexSink* sink, const float* faces, const fl
     P.chunk_base = (int32_t*)(ws + off[2]);
     P.chunk_desc = (uint4*)(ws + off[3]);
     P.chunk_out = (float2*)(ws + off[4]);
-    P.hmap = nullptr;
-    P.hmapT = nullptr;
     P.nz_cnt = nullptr;
     P.nz_pos = nullptr;
     P.nz_val = nullptr;
@@ -1309,27 +1359,36 @@ int sdn::rasterize_bwd_core(const VertexSink* sink, const float* faces, const fl
         hipError_t e = hipMemsetAsync(ws, 0, off[2], st);
         if (e != hipSuccess) return fail(SDN_ELAUNCH, "hipMemsetAsync(plan): %s", hipGetErrorString(e));
         // (every reserved chunk slot below the cap is written by k_edge_plan, valid or marked invalid: no 88 MB memset)
-        const bool sil_path = (P.flags & SDN_ALPHA) && !(P.flags & SDN_RGB) && !(flags & SDN_SERIAL_EDGES);
-        if (!sil_path) {   // (k_hmap sets the flags on its way over the face-index map)
+        // the fast path's set-up lives in space it owns anyway: the two coverage bit maps (rows of cov_words words) in the slot
+        // bs*S*S*4 bytes wide at off[6], the transposed upstream gradient (at most bs*S*S floats) at the head of own_rec.  Both
+        // fit for every S >= 2 (2 * cdiv(S, 32) <= S); a size at which they do not takes the general path.
+        const size_t cov_words = (size_t)(S + 31) / 32;
+        const bool setup_fits = 2 * (size_t)bs * S * cov_words * sizeof(uint32_t) <= off[7] - off[6] &&
+                                (size_t)bs * S * S * sizeof(float) <= off[12] - off[11];
+        const bool sil_path = (P.flags & SDN_ALPHA) && !(P.flags & SDN_RGB) && !(flags & SDN_SERIAL_EDGES) && setup_fits;
+        if (!sil_path) {   // (k_cover_bits sets the flags on its way over the face-index map)
             hipLaunchKernelGGL(k_mark_visible, dim3(cdiv(npx, 256)), dim3(256), 0, st, face_index_map, npx, S, nf,
                                P.visible);
             if ((rc = check_launch("k_mark_visible"))) return rc;
         }
         if (sil_path) {
-            float* hmap = (float*)(ws + off[5]);
-            float* hmapT = (float*)(ws + off[6]);
             if (S > 65535) return fail(SDN_EINVAL, "sdn_rasterize_bwd: internal size %d exceeds the 16-bit row index", S);
+            const bool aa = (P.flags & SDN_AA) != 0;
+            const size_t rows = (size_t)bs * S;
+            uint32_t* cov = (uint32_t*)(ws + off[6]);   // both bit maps in the slot of the former dense map (checked above)
+            uint32_t* covT = cov + rows * cov_words;
+            float* gT = (float*)(ws + off[11]);   // head of own_rec: k_edge_scan_sil, later on the stream, is its first writer
             uint16_t* cnt = (uint16_t*)(ws + off[7]);
             uint16_t* pos = (uint16_t*)(ws + off[8]);
             float* val = (float*)(ws + off[9]);
-            const size_t rows = (size_t)bs * S;
-            hipLaunchKernelGGL(k_hmap, dim3(cdiv(S, 32), cdiv(S, 32), bs), dim3(256), 0, st, P, hmapT);
-            if ((rc = check_launch("k_hmap"))) return rc;
-            hipLaunchKernelGGL(k_compact_rows, dim3((unsigned)cdiv((long)(2 * rows), 4)), dim3(256), 0, st, P, hmapT, rows, S, cnt, pos,
-                               val);
+            hipLaunchKernelGGL(k_cover_bits, dim3(cdiv(S, 32), cdiv(S, 32), bs), dim3(256), 0, st, P, cov, covT, gT);
+            if ((rc = check_launch("k_cover_bits"))) return rc;
+            const dim3 grid((unsigned)cdiv((long)(2 * rows), 4));
+            if (aa)
+                hipLaunchKernelGGL(k_compact_rows<true>, grid, dim3(256), 0, st, P, cov, covT, gT, rows, S, cnt, pos, val);
+            else
+                hipLaunchKernelGGL(k_compact_rows<false>, grid, dim3(256), 0, st, P, cov, covT, gT, rows, S, cnt, pos, val);
             if ((rc = check_launch("k_compact_rows"))) return rc;
-            P.hmap = hmap;
-            P.hmapT = hmapT;
             P.nz_cnt = cnt;
             P.nz_pos = pos;
             P.nz_val = val;
