@@ -21,6 +21,7 @@
 
 #include <climits>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -50,7 +51,6 @@ struct AsmPlanes {
     float mean, std, add;
 };
 
-__device__ __forceinline__ int asm_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // pixel (source row sy, scaled column xs) of the horizontally resampled plane, as the uint8 image Pillow's first pass stores
 __device__ __forceinline__ int asm_hpix(const AsmPlanes& A, const uint8_t* __restrict__ plane, int sy, int xs)
@@ -61,7 +61,7 @@ __device__ __forceinline__ int asm_hpix(const AsmPlanes& A, const uint8_t* __res
     const int* k = A.xk + (size_t)xs * A.xks;
     int acc = 1 << (ASM_BITS - 1);
     for (int t = 0; t < A.xks; t++) acc += (int)row[min(x0 + t, A.W - 1)] * k[t];
-    return asm_clip8(acc >> ASM_BITS);
+    return clip8(acc >> ASM_BITS);
 }
 
 __device__ __forceinline__ float asm_finish(const AsmPlanes& A, int v)
@@ -123,7 +123,7 @@ __global__ __launch_bounds__(ASM_THREADS) void k_assemble_planes(const AsmPlanes
                 const int* k = A.yk + (size_t)(y1 + y) * A.yks;
                 int acc = 1 << (ASM_BITS - 1);
                 for (int t = 0; t < A.yks; t++) acc += (int)s_rows[min(y0 + t, rows - 1) * w + wc] * k[t];
-                v = asm_finish(A, asm_clip8(acc >> ASM_BITS));
+                v = asm_finish(A, clip8(acc >> ASM_BITS));
             }
             out[(size_t)y * w + x] = v;
         }

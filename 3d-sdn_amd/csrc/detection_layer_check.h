@@ -1,6 +1,6 @@
 // Constants, the workspace layout and HOST argument validation of the detection layer (detection_layer.hip).  Plain C++ so that a host
 // program can walk the layout and the validators without the HIP runtime (tools/detection_layer_check.cpp).  The score's integer
-// image, the keys, the sorting network and the alignment test are the proposal layer's (proposal_layer_check.h).
+// image, the keys, the sorting network and the workspace's alignment are the proposal layer's (proposal_layer_check.h).
 #pragma once
 
 #include "proposal_layer_check.h"
@@ -20,7 +20,7 @@ constexpr int DET_HEAD_INTS = 4;                       // the valid count M, pad
 // first NaN winning.  True when the candidate (v, c) replaces (score, cls): a NaN before a number, the lower index of two NaNs, the
 // greater of two numbers, the lower index of two equal ones.  A walk in index order that starts from (-inf, INT_MAX) and the merge of
 // the candidates of several such walks over disjoint classes both use it, and both give the walk over all classes.
-PROP_HD bool det_argmax_takes(float score, int cls, float v, int c)
+SDN_HD bool det_argmax_takes(float score, int cls, float v, int c)
 {
     const bool mine_nan = score != score, other_nan = v != v;
     return other_nan ? (!mine_nan || c < cls) : (!mine_nan && (v > score || (v == score && c < cls)));
@@ -40,31 +40,31 @@ struct DetLayout {
 // 0 when (N, C, D) is a valid problem; otherwise 1 with the reason in msg
 inline int det_validate_sizes(int N, int C, int D, char* msg, size_t cap)
 {
-    if (N < 1 || N > DET_MAX_ROIS) PROP_FAIL("N %d; 1 to %d rois are supported (their keys are sorted in the LDS)", N, DET_MAX_ROIS);
-    if (C < 1) PROP_FAIL("bad sizes: C %d (no classes)", C);
-    if (D < 1 || D > DET_MAX_INSTANCES) PROP_FAIL("D %d; 1 to %d detections are supported", D, DET_MAX_INSTANCES);
+    if (N < 1 || N > DET_MAX_ROIS) SDN_FAIL("N %d; 1 to %d rois are supported (their keys are sorted in the LDS)", N, DET_MAX_ROIS);
+    if (C < 1) SDN_FAIL("bad sizes: C %d (no classes)", C);
+    if (D < 1 || D > DET_MAX_INSTANCES) SDN_FAIL("D %d; 1 to %d detections are supported", D, DET_MAX_INSTANCES);
     return 0;
 }
 
 inline int det_layout(int N, int C, int D, DetLayout* L, char* msg, size_t cap)
 {
     if (det_validate_sizes(N, C, D, msg, cap)) return 1;
-    if (!L) PROP_FAIL("the layout is NULL");
+    if (!L) SDN_FAIL("the layout is NULL");
     size_t at = 0;   // N <= 2^13: the largest range, the mask, is 2^13 * 2^7 * 8 = 8 MiB
     L->head = at;
-    at += prop_round(sizeof(int32_t) * (size_t)DET_HEAD_INTS);
+    at += round_up(sizeof(int32_t) * (size_t)DET_HEAD_INTS, PROP_ALIGN);
     L->keys = at;
-    at += prop_round(sizeof(uint64_t) * (size_t)N);
+    at += round_up(sizeof(uint64_t) * (size_t)N, PROP_ALIGN);
     L->boxes = at;
-    at += prop_round(4 * sizeof(float) * (size_t)N);
+    at += round_up(4 * sizeof(float) * (size_t)N, PROP_ALIGN);
     L->areas = at;
-    at += prop_round(sizeof(float) * (size_t)N);
+    at += round_up(sizeof(float) * (size_t)N, PROP_ALIGN);
     L->classes = at;
-    at += prop_round(sizeof(int32_t) * (size_t)N);
+    at += round_up(sizeof(int32_t) * (size_t)N, PROP_ALIGN);
     L->rows = at;
-    at += prop_round(sizeof(int32_t) * (size_t)N);
+    at += round_up(sizeof(int32_t) * (size_t)N, PROP_ALIGN);
     L->mask = at;
-    at += prop_round(sizeof(uint64_t) * (size_t)N * (size_t)prop_words(N));
+    at += round_up(sizeof(uint64_t) * (size_t)N * (size_t)prop_words(N), PROP_ALIGN);
     L->total = at;
     return 0;
 }
@@ -76,22 +76,22 @@ inline int det_validate(const void* rois, const void* probs, const void* deltas,
 {
     DetLayout L;
     if (det_layout(N, C, D, &L, msg, cap)) return 1;
-    if (height < 1 || width < 1) PROP_FAIL("bad sizes: image %d x %d", height, width);
-    if (!window) PROP_FAIL("window is NULL (four floats in host memory)");
-    if (!std_dev) PROP_FAIL("std_dev is NULL (four floats in host memory)");
-    if (!rois || !probs || !deltas) PROP_FAIL("rois, probs or deltas is NULL");
-    if (!class_ids || !scores || !boxes_px) PROP_FAIL("class_ids, scores or boxes_px is NULL");
-    if (!keep || !count || !detections || !boxes_norm) PROP_FAIL("keep, count, detections or boxes_norm is NULL");
-    if (!workspace) PROP_FAIL("workspace is NULL");
-    if (workspace_bytes < L.total) PROP_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
-    if (prop_misaligned(rois, 4) || prop_misaligned(probs, 4) || prop_misaligned(deltas, 4))
-        PROP_FAIL("rois, probs and deltas must be aligned to 4 bytes");
-    if (roi_count && prop_misaligned(roi_count, 4)) PROP_FAIL("roi_count must be aligned to 4 bytes");
-    if (prop_misaligned(class_ids, 4) || prop_misaligned(scores, 4) || prop_misaligned(keep, 4) || prop_misaligned(count, 4) ||
-        prop_misaligned(detections, 4))
-        PROP_FAIL("class_ids, scores, keep, count and detections must be aligned to 4 bytes");
-    if (prop_misaligned(boxes_px, 16) || prop_misaligned(boxes_norm, 16) || prop_misaligned(workspace, 16))
-        PROP_FAIL("boxes_px, boxes_norm and workspace must be aligned to 16 bytes");
+    if (height < 1 || width < 1) SDN_FAIL("bad sizes: image %d x %d", height, width);
+    if (!window) SDN_FAIL("window is NULL (four floats in host memory)");
+    if (!std_dev) SDN_FAIL("std_dev is NULL (four floats in host memory)");
+    if (!rois || !probs || !deltas) SDN_FAIL("rois, probs or deltas is NULL");
+    if (!class_ids || !scores || !boxes_px) SDN_FAIL("class_ids, scores or boxes_px is NULL");
+    if (!keep || !count || !detections || !boxes_norm) SDN_FAIL("keep, count, detections or boxes_norm is NULL");
+    if (!workspace) SDN_FAIL("workspace is NULL");
+    if (workspace_bytes < L.total) SDN_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
+    if (misaligned(rois, 4) || misaligned(probs, 4) || misaligned(deltas, 4))
+        SDN_FAIL("rois, probs and deltas must be aligned to 4 bytes");
+    if (roi_count && misaligned(roi_count, 4)) SDN_FAIL("roi_count must be aligned to 4 bytes");
+    if (misaligned(class_ids, 4) || misaligned(scores, 4) || misaligned(keep, 4) || misaligned(count, 4) ||
+        misaligned(detections, 4))
+        SDN_FAIL("class_ids, scores, keep, count and detections must be aligned to 4 bytes");
+    if (misaligned(boxes_px, 16) || misaligned(boxes_norm, 16) || misaligned(workspace, 16))
+        SDN_FAIL("boxes_px, boxes_norm and workspace must be aligned to 16 bytes");
     return 0;
 }
 

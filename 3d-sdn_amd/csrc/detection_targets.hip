@@ -27,14 +27,11 @@
 
 #include "crop_sample.h"
 #include "detection_targets_check.h"
+#include "device_common.h"
 #include "prop_device.h"
 #include "sdn_common.h"
 
 namespace sdn {
-
-// torch.max / torch.min of two tensors: a NaN on either side is the result
-__device__ __forceinline__ float dt_max(float a, float b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ float dt_min(float a, float b) { return (a < b || a != a) ? a : b; }
 
 struct DtSample {
     const float* proposals;    // [N, 4] normalised
@@ -103,9 +100,9 @@ __global__ __launch_bounds__(DT_THREADS) void k_dt_sample(const DtSample D)
                 if (kind == DT_KIND_DROPPED) continue;
                 const float4 b = s_box[g];
                 // bbox_overlaps, :524-539
-                const float y1 = dt_max(py1, b.x), x1 = dt_max(px1, b.y);
-                const float y2 = dt_min(py2, b.z), x2 = dt_min(px2, b.w);
-                const float inter = dt_max(x2 - x1, 0.0f) * dt_max(y2 - y1, 0.0f);
+                const float y1 = nan_first_max(py1, b.x), x1 = nan_first_max(px1, b.y);
+                const float y2 = nan_first_min(py2, b.z), x2 = nan_first_min(px2, b.w);
+                const float inter = nan_first_max(x2 - x1, 0.0f) * nan_first_max(y2 - y1, 0.0f);
                 const float uni = p_area + s_area[g] - inter;
                 const float iou = inter / uni;
                 if (kind == DT_KIND_GT) {

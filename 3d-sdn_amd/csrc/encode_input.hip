@@ -16,6 +16,7 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "encode_input_check.h"
 #include "sdn_common.h"
 
@@ -84,13 +85,6 @@ __device__ __forceinline__ void enc_store_planes(float* __restrict__ out, long H
     }
 }
 
-__device__ __forceinline__ int enc_wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // groups: N * H * (W / NP) groups of NP adjacent pixels of a row
 template <int NP>
 __global__ __launch_bounds__(ENC_THREADS) void k_encode_maps(const void* __restrict__ label, int label_dt, const void* __restrict__ inst,
@@ -156,8 +150,8 @@ __global__ __launch_bounds__(ENC_THREADS) void k_encode_maps(const void* __restr
         }
     }
     // every lane of the wave is here again: one atomic per wave, and only for a wave that met a bad index
-    bad_label = enc_wave_sum(bad_label);
-    bad_pose = enc_wave_sum(bad_pose);
+    bad_label = wave_sum(bad_label);
+    bad_pose = wave_sum(bad_pose);
     if ((threadIdx.x & 63) == 0) {
         if (bad_label) atomicAdd(&bad[0], bad_label);
         if (bad_pose) atomicAdd(&bad[1], bad_pose);
@@ -272,7 +266,7 @@ __global__ __launch_bounds__(ENC_THREADS) void k_inst_mark(void* __restrict__ in
     __syncthreads();
     for (int h = threadIdx.x; h < IDX_LDS_SLOTS; h += ENC_THREADS)
         if (bits_of[h]) atomicOr(&bitmap[word_of[h]], bits_of[h]);
-    over = enc_wave_sum(over);
+    over = wave_sum(over);
     if ((threadIdx.x & 63) == 0 && over) atomicAdd(&head[1], over);
 }
 

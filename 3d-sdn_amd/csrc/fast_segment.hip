@@ -16,6 +16,7 @@
 // gradient).  HBM-bound: 2 reads + 1 write of the [N, C, H, W] map.
 #include <hip/hip_runtime.h>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -99,8 +100,7 @@ __global__ __launch_bounds__(64) void k_segment_partial(const float* __restrict_
                 const int kk = __shfl(kv[j], __ffsll((long long)todo) - 1, 64);
                 const bool mine = kv[j] == kk;
                 const unsigned long long match = __ballot(mine);
-                float s = mine ? vv[j] : 0.f;
-                for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+                const float s = wave_sum(mine ? vv[j] : 0.f);
                 if (lane == 0) {
                     s_tab[kk] += s;
                     if (count) s_cnt[kk] += (float)__popcll(match);

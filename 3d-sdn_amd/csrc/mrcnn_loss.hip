@@ -17,47 +17,11 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "mrcnn_loss_check.h"
 #include "sdn_common.h"
 
 namespace sdn {
-
-__device__ __forceinline__ int mrl_wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double mrl_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ double mrl_wave_max(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const double t = __shfl_xor(v, o, 64);
-        v = t > v ? t : v;
-    }
-    return v;
-}
-
-// the lanes below this one: the sum of their v; total: the wave's
-__device__ __forceinline__ int mrl_wave_before(int v, int lane, int& total)
-{
-    int incl = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(incl, o, 64);
-        incl += lane >= o ? t : 0;
-    }
-    total = __shfl(incl, 63, 64);
-    return incl - v;
-}
 
 __device__ __forceinline__ void mrl_load4(const float* __restrict__ p, bool vec, float (&v)[4])
 {
@@ -183,7 +147,7 @@ __global__ __launch_bounds__(MRL_THREADS) void k_mrl_count(const void* __restric
         mrl_kinds(match, i64, vec, mrl_quad_first(chunk, s, lane), A, kind);
         n += mrl_positives(kind);
     }
-    n = mrl_wave_sum(n);
+    n = wave_sum(n);
     if (lane == 0) table[chunk] = n;
 }
 
@@ -192,7 +156,7 @@ __device__ __forceinline__ void mrl_rpn_partial(const MrlRpn& q, int chunk, int 
 {
     int before = 0;
     for (int i = lane; i < chunk; i += MRL_THREADS) before += table[i];
-    before = mrl_wave_sum(before);
+    before = wave_sum(before);
     if (lane == 0) prefix[chunk] = before;
     double s_cls = 0.0, s_box = 0.0;
     int valid = 0, used = 0, bad = 0;
@@ -200,7 +164,7 @@ __device__ __forceinline__ void mrl_rpn_partial(const MrlRpn& q, int chunk, int 
         const long a0 = mrl_quad_first(chunk, s, lane);
         int kind[4], total;
         mrl_kinds(q.match, q.match_i64, q.vec, a0, q.A, kind);
-        int rank = before + mrl_wave_before(mrl_positives(kind), lane, total);
+        int rank = before + wave_exclusive_sum(mrl_positives(kind), lane, total);
         before += total;
         if (a0 >= q.A) continue;
         float x[8];
@@ -228,11 +192,11 @@ __device__ __forceinline__ void mrl_rpn_partial(const MrlRpn& q, int chunk, int 
             }
         }
     }
-    s_cls = mrl_wave_sum(s_cls);
-    s_box = mrl_wave_sum(s_box);
-    valid = mrl_wave_sum(valid);
-    used = mrl_wave_sum(used);
-    bad = mrl_wave_sum(bad);
+    s_cls = wave_sum(s_cls);
+    s_box = wave_sum(s_box);
+    valid = wave_sum(valid);
+    used = wave_sum(used);
+    bad = wave_sum(bad);
     if (lane == 0) {
         psum[0] = s_cls; psum[1] = s_box; psum[2] = 0.0;
         pcnt[0] = valid; pcnt[1] = used; pcnt[2] = bad; pcnt[3] = 0;
@@ -248,8 +212,8 @@ __device__ __forceinline__ void mrl_roi_partial(const MrlHead& q, int r, int lan
     const float* row = q.logits + (long)r * q.C;
     const double ninf = -__builtin_huge_val();
     const double x0 = lane < q.C ? (double)row[lane] : ninf, x1 = lane + 64 < q.C ? (double)row[lane + 64] : ninf;
-    const double m = mrl_wave_max(x0 > x1 ? x0 : x1);
-    const double lse = m + log(mrl_wave_sum(exp(x0 - m) + exp(x1 - m)));
+    const double m = wave_max_greater(x0 > x1 ? x0 : x1);
+    const double lse = m + log(wave_sum(exp(x0 - m) + exp(x1 - m)));
     double s_cls = 0.0, s_box = 0.0, s_mask = 0.0;
     if (kind >= 0) s_cls = lse - (double)row[id];
     if (kind == 1) {
@@ -273,7 +237,7 @@ __device__ __forceinline__ void mrl_roi_partial(const MrlHead& q, int r, int lan
         } else {
             for (long i = lane; i < q.HW; i += MRL_THREADS) s_mask += mrl_bce(pm[i], ym[i]);
         }
-        s_mask = mrl_wave_sum(s_mask);
+        s_mask = wave_sum(s_mask);
     }
     if (lane == 0) {
         lse_out[r] = lse;
@@ -319,9 +283,9 @@ __global__ __launch_bounds__(64) void k_mrl_finish(const void* __restrict__ work
         }
     }
 #pragma unroll
-    for (int i = 0; i < 5; i++) s[i] = mrl_wave_sum(s[i]);
+    for (int i = 0; i < 5; i++) s[i] = wave_sum(s[i]);
 #pragma unroll
-    for (int i = 0; i < 6; i++) n[i] = mrl_wave_sum(n[i]);
+    for (int i = 0; i < 6; i++) n[i] = wave_sum(n[i]);
     if (threadIdx.x == 0) {
         // torch's means: 0 / 0 = NaN over an empty selection; with R = 0 the head losses are 0 (model.py:1070, 1088, 1118)
         double l[5];
@@ -353,7 +317,7 @@ __device__ __forceinline__ void mrl_rpn_grad(const MrlRpn& q, const MrlGrads& g,
         const long a0 = mrl_quad_first(chunk, s, lane);
         int kind[4], total;
         mrl_kinds(q.match, q.match_i64, q.vec, a0, q.A, kind);
-        int rank = before + mrl_wave_before(mrl_positives(kind), lane, total);
+        int rank = before + wave_exclusive_sum(mrl_positives(kind), lane, total);
         before += total;
         if (a0 >= q.A) continue;
         const bool full = a0 + MRL_QUAD <= q.A;

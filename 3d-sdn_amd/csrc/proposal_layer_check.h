@@ -9,17 +9,7 @@
 #include <cstdio>
 #include <cstring>
 
-#if defined(__HIPCC__)
-#define PROP_HD __host__ __device__ __forceinline__
-#else
-#define PROP_HD inline
-#endif
-
-#define PROP_FAIL(...)                        \
-    do {                                      \
-        std::snprintf(msg, cap, __VA_ARGS__); \
-        return 1;                             \
-    } while (0)
+#include "check_common.h"
 
 namespace sdn {
 
@@ -33,7 +23,7 @@ constexpr int PROP_ALIGN = 16;               // every range of the workspace sta
 
 // Order-preserving integer image of a score: a < b as floats <=> image(a) < image(b) as unsigned, with torch's sort order at the
 // ends: -0.0 and +0.0 are one value, every NaN is one value above +inf (torch.sort(descending=True) puts NaN first).
-PROP_HD uint32_t prop_image(uint32_t bits)
+SDN_HD uint32_t prop_image(uint32_t bits)
 {
     if ((bits & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;   // NaN, whatever its sign and payload
     if ((bits & 0x7fffffffu) == 0u) return 0x80000000u;           // both zeros
@@ -41,12 +31,12 @@ PROP_HD uint32_t prop_image(uint32_t bits)
 }
 
 // The 64-bit key of anchor `index`: descending keys are descending scores, equal scores lower index first.  Never 0.
-PROP_HD uint64_t prop_key(uint32_t image, uint32_t index) { return ((uint64_t)image << 32) | (uint64_t)(0xffffffffu - index); }
-PROP_HD uint32_t prop_key_index(uint64_t key) { return 0xffffffffu - (uint32_t)(key & 0xffffffffull); }
+SDN_HD uint64_t prop_key(uint32_t image, uint32_t index) { return ((uint64_t)image << 32) | (uint64_t)(0xffffffffu - index); }
+SDN_HD uint32_t prop_key_index(uint64_t key) { return 0xffffffffu - (uint32_t)(key & 0xffffffffull); }
 
-PROP_HD int prop_chunks(int A) { return (A + PROP_CHUNK - 1) / PROP_CHUNK; }
-PROP_HD int prop_words(int K) { return (K + 63) / 64; }
-PROP_HD int prop_sort_size(int K)   // the bitonic network's size: the power of two at or above K
+SDN_HD int prop_chunks(int A) { return (A + PROP_CHUNK - 1) / PROP_CHUNK; }
+SDN_HD int prop_words(int K) { return (K + 63) / 64; }
+SDN_HD int prop_sort_size(int K)   // the bitonic network's size: the power of two at or above K
 {
     int n = 1;
     while (n < K) n <<= 1;
@@ -55,14 +45,12 @@ PROP_HD int prop_sort_size(int K)   // the bitonic network's size: the power of 
 
 // Step (k, j) of the bitonic network over N = 2^m keys: compare-exchange t (0 .. N/2 - 1) touches the elements i < l = i + j, and
 // leaves the larger one first where `descending`.  The last merge (k = N) is descending throughout: best key first.
-PROP_HD void prop_bitonic_pair(int t, int j, int k, int* i, int* l, bool* descending)
+SDN_HD void prop_bitonic_pair(int t, int j, int k, int* i, int* l, bool* descending)
 {
     *i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
     *l = *i | j;
     *descending = (*i & k) == 0;
 }
-
-inline bool prop_misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
 
 struct PropLayout {
     size_t head;    // int32 [PROP_HEAD_INTS]: histograms of the four radix passes, then the cursor
@@ -73,34 +61,32 @@ struct PropLayout {
     size_t total;
 };
 
-inline size_t prop_round(size_t n) { return (n + PROP_ALIGN - 1) / PROP_ALIGN * PROP_ALIGN; }
-
 // 0 when (A, K, P) is a valid problem; otherwise 1 with the reason in msg
 inline int prop_validate_sizes(int A, int K, int P, char* msg, size_t cap)
 {
-    if (A < 1) PROP_FAIL("bad sizes: A %d (no anchors)", A);
-    if (A >= PROP_MAX_ANCHORS) PROP_FAIL("A %d; fewer than 2^24 = %d anchors are supported", A, PROP_MAX_ANCHORS);
-    if (K < 1 || K > PROP_MAX_PRE_NMS) PROP_FAIL("K %d; 1 to %d are supported (the selected keys are sorted in the LDS)", K, PROP_MAX_PRE_NMS);
-    if (K > A) PROP_FAIL("K %d exceeds A %d: K = min(pre_nms_limit, A)", K, A);
-    if (P < 1 || P > PROP_MAX_PRE_NMS) PROP_FAIL("P %d; 1 to %d are supported", P, PROP_MAX_PRE_NMS);
+    if (A < 1) SDN_FAIL("bad sizes: A %d (no anchors)", A);
+    if (A >= PROP_MAX_ANCHORS) SDN_FAIL("A %d; fewer than 2^24 = %d anchors are supported", A, PROP_MAX_ANCHORS);
+    if (K < 1 || K > PROP_MAX_PRE_NMS) SDN_FAIL("K %d; 1 to %d are supported (the selected keys are sorted in the LDS)", K, PROP_MAX_PRE_NMS);
+    if (K > A) SDN_FAIL("K %d exceeds A %d: K = min(pre_nms_limit, A)", K, A);
+    if (P < 1 || P > PROP_MAX_PRE_NMS) SDN_FAIL("P %d; 1 to %d are supported", P, PROP_MAX_PRE_NMS);
     return 0;
 }
 
 inline int prop_layout(int A, int K, int P, PropLayout* L, char* msg, size_t cap)
 {
     if (prop_validate_sizes(A, K, P, msg, cap)) return 1;
-    if (!L) PROP_FAIL("the layout is NULL");
+    if (!L) SDN_FAIL("the layout is NULL");
     size_t at = 0;   // A < 2^24, K <= 2^13: the largest range, the mask, is 2^13 * 2^7 * 8 = 8 MiB
     L->head = at;
-    at += prop_round(sizeof(int32_t) * (size_t)PROP_HEAD_INTS);
+    at += round_up(sizeof(int32_t) * (size_t)PROP_HEAD_INTS, PROP_ALIGN);
     L->ties = at;
-    at += prop_round(sizeof(int32_t) * (size_t)prop_chunks(A));
+    at += round_up(sizeof(int32_t) * (size_t)prop_chunks(A), PROP_ALIGN);
     L->keys = at;
-    at += prop_round(sizeof(uint64_t) * (size_t)K);
+    at += round_up(sizeof(uint64_t) * (size_t)K, PROP_ALIGN);
     L->areas = at;
-    at += prop_round(sizeof(float) * (size_t)K);
+    at += round_up(sizeof(float) * (size_t)K, PROP_ALIGN);
     L->mask = at;
-    at += prop_round(sizeof(uint64_t) * (size_t)K * (size_t)prop_words(K));
+    at += round_up(sizeof(uint64_t) * (size_t)K * (size_t)prop_words(K), PROP_ALIGN);
     L->total = at;
     return 0;
 }
@@ -111,17 +97,17 @@ inline int prop_validate(const void* rpn_probs, const void* rpn_bbox, const void
 {
     PropLayout L;
     if (prop_layout(A, K, P, &L, msg, cap)) return 1;
-    if (height < 1 || width < 1) PROP_FAIL("bad sizes: image %d x %d", height, width);
-    if (!std_dev) PROP_FAIL("std_dev is NULL (four floats in host memory)");
-    if (!rpn_probs || !rpn_bbox || !anchors) PROP_FAIL("rpn_probs, rpn_bbox or anchors is NULL");
-    if (!order || !boxes_px || !keep || !count || !rois) PROP_FAIL("order, boxes_px, keep, count or rois is NULL");
-    if (!workspace) PROP_FAIL("workspace is NULL");
-    if (workspace_bytes < L.total) PROP_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
-    if (prop_misaligned(rpn_probs, 4) || prop_misaligned(rpn_bbox, 4) || prop_misaligned(anchors, 4))
-        PROP_FAIL("rpn_probs, rpn_bbox and anchors must be aligned to 4 bytes");
-    if (prop_misaligned(order, 4) || prop_misaligned(keep, 4) || prop_misaligned(count, 4)) PROP_FAIL("order, keep and count must be aligned to 4 bytes");
-    if (prop_misaligned(boxes_px, 16) || prop_misaligned(rois, 16) || prop_misaligned(workspace, 16))
-        PROP_FAIL("boxes_px, rois and workspace must be aligned to 16 bytes");
+    if (height < 1 || width < 1) SDN_FAIL("bad sizes: image %d x %d", height, width);
+    if (!std_dev) SDN_FAIL("std_dev is NULL (four floats in host memory)");
+    if (!rpn_probs || !rpn_bbox || !anchors) SDN_FAIL("rpn_probs, rpn_bbox or anchors is NULL");
+    if (!order || !boxes_px || !keep || !count || !rois) SDN_FAIL("order, boxes_px, keep, count or rois is NULL");
+    if (!workspace) SDN_FAIL("workspace is NULL");
+    if (workspace_bytes < L.total) SDN_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
+    if (misaligned(rpn_probs, 4) || misaligned(rpn_bbox, 4) || misaligned(anchors, 4))
+        SDN_FAIL("rpn_probs, rpn_bbox and anchors must be aligned to 4 bytes");
+    if (misaligned(order, 4) || misaligned(keep, 4) || misaligned(count, 4)) SDN_FAIL("order, keep and count must be aligned to 4 bytes");
+    if (misaligned(boxes_px, 16) || misaligned(rois, 16) || misaligned(workspace, 16))
+        SDN_FAIL("boxes_px, rois and workspace must be aligned to 16 bytes");
     return 0;
 }
 

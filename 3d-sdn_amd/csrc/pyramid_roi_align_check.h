@@ -9,17 +9,7 @@
 #include <cstdint>
 #include <cstdio>
 
-#if defined(__HIPCC__)
-#define PRA_HD __host__ __device__ __forceinline__
-#else
-#define PRA_HD inline
-#endif
-
-#define PRA_FAIL(...)                         \
-    do {                                      \
-        std::snprintf(msg, cap, __VA_ARGS__); \
-        return 1;                             \
-    } while (0)
+#include "check_common.h"
 
 namespace sdn {
 
@@ -30,13 +20,13 @@ constexpr int PRA_MAX_POOL = 32;      // the sample table of pool x pool entries
 constexpr int PRA_SAMPLE_BYTES = 28;  // four tap offsets (int), two lerp weights (float), an inside flag (int)
 constexpr int PRA_ALIGN_FLOATS = 4;   // every level's gradient range starts on 16 bytes: the zero fill stores 16 bytes at a time
 
-PRA_HD int pra_chunks(int C) { return (C + PRA_CHANNELS - 1) / PRA_CHANNELS; }
-PRA_HD size_t pra_table_bytes(int pool) { return (size_t)pool * (size_t)pool * PRA_SAMPLE_BYTES; }
+SDN_HD int pra_chunks(int C) { return (C + PRA_CHANNELS - 1) / PRA_CHANNELS; }
+SDN_HD size_t pra_table_bytes(int pool) { return (size_t)pool * (size_t)pool * PRA_SAMPLE_BYTES; }
 
 // model.py:456-457 on the value of :455: round half to even (torch.round, rintf in the default rounding mode), then clamp to [2, 5].
 // A non-finite value -- a box of area <= 0 gives log(0) = -inf or sqrt(< 0) = NaN -- gives level 2: the reference's .int() of such a
 // float is INT_MIN on x86 (cvttss2si's "integer indefinite"), which the clamp lifts to 2, for +inf and NaN as for -inf.
-PRA_HD int pra_level_of(float v)
+SDN_HD int pra_level_of(float v)
 {
     if (!(v - v == 0.0f)) return 2;   // NaN, +inf, -inf
     const float r = rintf(v);
@@ -44,24 +34,22 @@ PRA_HD int pra_level_of(float v)
 }
 
 // model.py:445-455 with log2 of :95-100, operation for operation in fp32; image_area = float(image_shape[0] * image_shape[1])
-PRA_HD float pra_level_value(float y1, float x1, float y2, float x2, float image_area)
+SDN_HD float pra_level_value(float y1, float x1, float y2, float x2, float image_area)
 {
     const float h = y2 - y1, w = x2 - x1;
     return 4.0f + logf(sqrtf(h * w) / (224.0f / sqrtf(image_area))) / logf(2.0f);
 }
 
-inline bool pra_misaligned(const void* p, unsigned a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) != 0; }
-
 // 0 when the sizes of sdn_pyramid_roi_align_fwd / _bwd / _grad_floats are valid; otherwise 1 with the reason in msg
 inline int pra_validate_maps(int C, const int* H, const int* W, char* msg, size_t cap)
 {
-    if (!H || !W) PRA_FAIL("H or W is NULL");
-    if (C <= 0) PRA_FAIL("bad sizes: C %d", C);
+    if (!H || !W) SDN_FAIL("H or W is NULL");
+    if (C <= 0) SDN_FAIL("bad sizes: C %d", C);
     for (int l = 0; l < PRA_LEVELS; l++) {
-        if (H[l] <= 0 || W[l] <= 0) PRA_FAIL("bad sizes: level P%d is %d x %d", l + 2, H[l], W[l]);
+        if (H[l] <= 0 || W[l] <= 0) SDN_FAIL("bad sizes: level P%d is %d x %d", l + 2, H[l], W[l]);
         // no product overflows: every factor is below 2^31 and the running product is checked before the next factor
         const long long hw = (long long)H[l] * (long long)W[l];
-        if (hw > INT_MAX || hw * C > INT_MAX) PRA_FAIL("C * H * W = %d * %d * %d of level P%d must stay below 2^31", C, H[l], W[l], l + 2);
+        if (hw > INT_MAX || hw * C > INT_MAX) SDN_FAIL("C * H * W = %d * %d * %d of level P%d must stay below 2^31", C, H[l], W[l], l + 2);
     }
     return 0;
 }
@@ -70,7 +58,7 @@ inline int pra_validate_maps(int C, const int* H, const int* W, char* msg, size_
 inline int pra_grad_layout(int C, const int* H, const int* W, size_t offsets[PRA_LEVELS], size_t* total, char* msg, size_t cap)
 {
     if (pra_validate_maps(C, H, W, msg, cap)) return 1;
-    if (!offsets || !total) PRA_FAIL("offsets or total is NULL");
+    if (!offsets || !total) SDN_FAIL("offsets or total is NULL");
     size_t at = 0;
     for (int l = 0; l < PRA_LEVELS; l++) {
         offsets[l] = at;
@@ -83,13 +71,13 @@ inline int pra_grad_layout(int C, const int* H, const int* W, size_t offsets[PRA
 
 inline int pra_validate_sizes(int R, int C, const int* H, const int* W, int pool, float image_area, char* msg, size_t cap)
 {
-    if (R < 0) PRA_FAIL("bad sizes: R %d", R);
+    if (R < 0) SDN_FAIL("bad sizes: R %d", R);
     if (pra_validate_maps(C, H, W, msg, cap)) return 1;
-    if (pool <= 0 || pool > PRA_MAX_POOL) PRA_FAIL("pool %d; 1 to %d are supported (the sample table lives in the LDS)", pool, PRA_MAX_POOL);
-    if (!(image_area - image_area == 0.0f) || image_area <= 0.0f) PRA_FAIL("image_area %g must be finite and positive", (double)image_area);
+    if (pool <= 0 || pool > PRA_MAX_POOL) SDN_FAIL("pool %d; 1 to %d are supported (the sample table lives in the LDS)", pool, PRA_MAX_POOL);
+    if (!(image_area - image_area == 0.0f) || image_area <= 0.0f) SDN_FAIL("image_area %g must be finite and positive", (double)image_area);
     const long long per_box = (long long)C * pool * pool;   // C < 2^31, pool <= 32
-    if (per_box > INT_MAX) PRA_FAIL("C * pool * pool = %d * %d * %d must stay below 2^31", C, pool, pool);
-    if ((long long)R * pra_chunks(C) > INT_MAX) PRA_FAIL("R * ceil(C / %d) = %d * %d workgroups must stay below 2^31", PRA_CHANNELS, R, pra_chunks(C));
+    if (per_box > INT_MAX) SDN_FAIL("C * pool * pool = %d * %d * %d must stay below 2^31", C, pool, pool);
+    if ((long long)R * pra_chunks(C) > INT_MAX) SDN_FAIL("R * ceil(C / %d) = %d * %d workgroups must stay below 2^31", PRA_CHANNELS, R, pra_chunks(C));
     return 0;
 }
 
@@ -98,13 +86,13 @@ inline int pra_validate_fwd(const void* boxes, const void* const* maps, const in
 {
     if (pra_validate_sizes(R, C, H, W, pool, image_area, msg, cap)) return 1;
     if (R == 0) return 0;   // nothing is read or written
-    if (!boxes || !pooled || !levels) PRA_FAIL("boxes, pooled or levels is NULL with R > 0");
-    if (!maps) PRA_FAIL("maps is NULL with R > 0");
+    if (!boxes || !pooled || !levels) SDN_FAIL("boxes, pooled or levels is NULL with R > 0");
+    if (!maps) SDN_FAIL("maps is NULL with R > 0");
     for (int l = 0; l < PRA_LEVELS; l++) {
-        if (!maps[l]) PRA_FAIL("the map of level P%d is NULL with R > 0", l + 2);
-        if (pra_misaligned(maps[l], 4)) PRA_FAIL("the maps must be aligned to 4 bytes");
+        if (!maps[l]) SDN_FAIL("the map of level P%d is NULL with R > 0", l + 2);
+        if (misaligned(maps[l], 4)) SDN_FAIL("the maps must be aligned to 4 bytes");
     }
-    if (pra_misaligned(boxes, 4) || pra_misaligned(pooled, 4) || pra_misaligned(levels, 4)) PRA_FAIL("boxes, pooled and levels must be aligned to 4 bytes");
+    if (misaligned(boxes, 4) || misaligned(pooled, 4) || misaligned(levels, 4)) SDN_FAIL("boxes, pooled and levels must be aligned to 4 bytes");
     return 0;
 }
 
@@ -112,11 +100,11 @@ inline int pra_validate_bwd(const void* grads, const void* boxes, const int* H, 
                             const void* grad_maps, char* msg, size_t cap)
 {
     if (pra_validate_sizes(R, C, H, W, pool, image_area, msg, cap)) return 1;
-    if (!grad_maps) PRA_FAIL("grad_maps is NULL");   // zero-filled for R = 0 too
-    if (pra_misaligned(grad_maps, 16)) PRA_FAIL("grad_maps must be aligned to 16 bytes");
+    if (!grad_maps) SDN_FAIL("grad_maps is NULL");   // zero-filled for R = 0 too
+    if (misaligned(grad_maps, 16)) SDN_FAIL("grad_maps must be aligned to 16 bytes");
     if (R == 0) return 0;
-    if (!grads || !boxes) PRA_FAIL("grads or boxes is NULL with R > 0");
-    if (pra_misaligned(grads, 4) || pra_misaligned(boxes, 4)) PRA_FAIL("grads and boxes must be aligned to 4 bytes");
+    if (!grads || !boxes) SDN_FAIL("grads or boxes is NULL with R > 0");
+    if (misaligned(grads, 4) || misaligned(boxes, 4)) SDN_FAIL("grads and boxes must be aligned to 4 bytes");
     return 0;
 }
 

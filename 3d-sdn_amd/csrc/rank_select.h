@@ -5,10 +5,12 @@
 
 #include <cstdint>
 
+#include "device_common.h"
+
 namespace sdn {
 
 // The bin of a 256-bin histogram that holds the element of rank `rank` (zero-based, ascending) and the rank inside that bin,
-// by one wave: four bins per lane, an inclusive scan over the lanes.  (0, 0) when the histogram holds fewer elements.
+// by one wave: four bins per lane, an exclusive scan over the lanes.  (0, 0) when the histogram holds fewer elements.
 __device__ __forceinline__ void ids_find(const int32_t* hist, long rank, int lane, int* bin, int* residual)
 {
     int c[4];
@@ -17,12 +19,10 @@ __device__ __forceinline__ void ids_find(const int32_t* hist, long rank, int lan
         c[k] = hist[4 * lane + k];
         sum += c[k];
     }
-    int incl = sum;
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(incl, d, 64);
-        if (lane >= d) incl += t;
-    }
-    long before = incl - sum;
+    int total;   // not needed: a rank past every bin finds nothing
+    const int below = wave_exclusive_sum(sum, lane, total);
+    const int incl = below + sum;
+    long before = below;
     int b = 0, r = 0;
     bool found = false;
     if (rank >= before && rank < incl) {

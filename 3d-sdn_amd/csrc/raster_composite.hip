@@ -8,6 +8,7 @@
 // Compiled without FMA contraction: results are bit-identical to the PIL path (tests/test_gpu_composite.py).
 #include <hip/hip_runtime.h>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -18,7 +19,6 @@ struct CompObj {  // one row of the host's object table
     int idx, size, left, top, boff, koff, ksize;
 };
 
-__device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // torchvision to_pil_image on a float tensor: pic.mul(255).byte()
 __device__ __forceinline__ int u8_mask(float v) { return (int)(unsigned char)(int)(v * 255.f); }

@@ -33,15 +33,12 @@
 // bits.  log is the only operation whose last bit can differ from the reference's CPU run.
 #include <hip/hip_runtime.h>
 
+#include "device_common.h"
 #include "rank_select.h"
 #include "rpn_targets_check.h"
 #include "sdn_common.h"
 
 namespace sdn {
-
-// np.maximum / np.minimum / np.amax: a NaN on either side is the result
-__device__ __forceinline__ double rt_max(double a, double b) { return (a > b || a != a) ? a : b; }
-__device__ __forceinline__ double rt_min(double a, double b) { return (a < b || a != a) ? a : b; }
 
 constexpr int RT_KIND_DROPPED = 0, RT_KIND_BOX = 1, RT_KIND_CROWD = 2;
 
@@ -120,13 +117,13 @@ __global__ __launch_bounds__(RT_MATCH_THREADS) void k_rt_match(const RtArgs R)
             const int kind = s_kind[g];   // the same in every lane
             if (kind == RT_KIND_DROPPED) continue;
             // compute_iou, utils.py:63-69: the box is the ground truth's, the boxes are the anchors
-            const double y1 = rt_max(s_box[g][0], a0), y2 = rt_min(s_box[g][2], a2);
-            const double x1 = rt_max(s_box[g][1], a1), x2 = rt_min(s_box[g][3], a3);
-            const double inter = rt_max(x2 - x1, 0.0) * rt_max(y2 - y1, 0.0);
+            const double y1 = nan_first_max(s_box[g][0], a0), y2 = nan_first_min(s_box[g][2], a2);
+            const double x1 = nan_first_max(s_box[g][1], a1), x2 = nan_first_min(s_box[g][3], a3);
+            const double inter = nan_first_max(x2 - x1, 0.0) * nan_first_max(y2 - y1, 0.0);
             const double uni = s_area[g] + a_area - inter;
             const double iou = inter / uni;
             if (kind == RT_KIND_CROWD) {   // :1244 np.amax
-                crowd_best = have_crowd ? rt_max(crowd_best, iou) : iou;
+                crowd_best = have_crowd ? nan_first_max(crowd_best, iou) : iou;
                 have_crowd = true;
                 continue;
             }

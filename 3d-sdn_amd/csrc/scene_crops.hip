@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -60,7 +61,6 @@ struct CropParams {
 
 enum { KIND_RGB = 1, KIND_MASK = 2, KIND_IGNORE = 4 };
 
-__device__ __forceinline__ int crop_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // pixel (wy, wx) of object n's square window, as the uint8 image crop_square returns holds it.  plane 0..2: image channel,
 // 3: mask, 4: ignore.  Every global read is behind the frame test.
@@ -135,7 +135,7 @@ __global__ __launch_bounds__(CROP_THREADS) void k_scene_crops(const CropParams A
             const int x0 = b[2 * x], xc = b[2 * x + 1];
             int acc = 1 << (CROP_BITS - 1);
             for (int t = 0; t < xc; t++) acc += crop_source(A, o, n, plane, ybase + ry, x0 + t) * k[x * ksize + t];
-            s_rows[i] = (uint8_t)crop_clip8(acc >> CROP_BITS);
+            s_rows[i] = (uint8_t)clip8(acc >> CROP_BITS);
         }
         __syncthreads();
         // vertical pass, to_tensor, Normalize
@@ -147,7 +147,7 @@ __global__ __launch_bounds__(CROP_THREADS) void k_scene_crops(const CropParams A
                 const int row = min(y0 + t, cap - 1);
                 acc += (int)s_rows[row * S + x] * k[y * ksize + t];
             }
-            float v = (float)crop_clip8(acc >> CROP_BITS) / 255.f;
+            float v = (float)clip8(acc >> CROP_BITS) / 255.f;
             if (img) v = (v - mean) / sd;
             out[(size_t)y * S + x] = v;
         }

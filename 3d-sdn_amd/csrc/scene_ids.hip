@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "device_common.h"
 #include "rank_select.h"
 #include "sdn_common.h"
 
@@ -47,17 +48,6 @@ constexpr size_t ID_WS_LO = ID_WS_SEL + (size_t)ID_OBJS * 4;
 constexpr size_t ID_WS_INTS = ID_WS_LO + (size_t)ID_OBJS * 2 * ID_BINS;
 static_assert(ID_THREADS == ID_BINS, "a workgroup flushes one bin per thread");
 static_assert((ID_SLOTS & (ID_SLOTS - 1)) == 0, "slots are probed modulo a power of two");
-
-__device__ __forceinline__ int ids_wave_min(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int ids_wave_max(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
 
 __global__ __launch_bounds__(256) void k_ids_init(int32_t* table, int32_t* ws)
 {
@@ -150,8 +140,8 @@ __global__ __launch_bounds__(ID_THREADS) void k_ids_pass_a(const int32_t* __rest
             int slot = -1;
             if (lane == src) slot = ids_slot(s_key, j0);
             slot = __shfl(slot, src, 64);
-            const int ymin = ids_wave_min(mine ? y : INT_MAX), xmin = ids_wave_min(mine ? x : INT_MAX);
-            const int ymax = ids_wave_max(mine ? y : -1), xmax = ids_wave_max(mine ? x : -1);
+            const int ymin = wave_imin(mine ? y : INT_MAX), xmin = wave_imin(mine ? x : INT_MAX);
+            const int ymax = wave_imax(mine ? y : -1), xmax = wave_imax(mine ? x : -1);
             const bool nz = mine && d != 0;
             unsigned long long left = __ballot(nz);
             if (lane == src) {
@@ -277,17 +267,6 @@ __global__ __launch_bounds__(64) void k_ids_pick(int32_t* table, const int32_t* 
     }
 }
 
-// the words [e0, e0 + 4) of an array whose word 0 is 16-byte aligned; only [lo, hi) is written
-__device__ __forceinline__ void ids_store_quad(uint32_t* base, long e0, long lo, long hi, const uint32_t vals[4])
-{
-    if (e0 >= lo && e0 + 4 <= hi) {
-        *reinterpret_cast<uint4*>(base + e0) = make_uint4(vals[0], vals[1], vals[2], vals[3]);
-    } else {
-        for (int j = 0; j < 4; j++)
-            if (e0 + j >= lo && e0 + j < hi) base[e0 + j] = vals[j];
-    }
-}
-
 // blockIdx.y names an output row of H W words: mask plane k, ignore plane k or cover chunk c; a thread owns an aligned quad
 // of it.  The rows are addressed from the first 16-byte aligned word at or below the array (H W need not be a multiple of 4,
 // and the array may start inside a quad): a quad across two rows is written in part by a thread of either.
@@ -333,7 +312,7 @@ __global__ __launch_bounds__(256) void k_ids_planes(const int32_t* __restrict__ 
             for (int j = 0; j < 4; j++) vals[j] |= (v[j] > t ? 1u : 0u) << k;
         }
     }
-    ids_store_quad(base, e0, lo, hi, vals);
+    store_quad(base, e0, lo, hi, vals);
 }
 
 static bool ids_debug_checks()

@@ -18,6 +18,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -51,45 +52,6 @@ struct UnmoldParams {
     float* masks;                  // [n, 1, H, W] or null
     int32_t* areas;                // [n] or null (zeroed by the launcher)
 };
-
-__device__ __forceinline__ int um_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-__device__ __forceinline__ float wave_min(float v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = fminf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = fmaxf(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_sum(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_imin(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int wave_imax(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
-}
-
-// `vals` of the elements [e0, e0 + 4) of a float array whose element 0 is 16-byte aligned; only [lo, hi) is written.
-__device__ __forceinline__ void store_quad(float* base, long e0, long lo, long hi, const float vals[4])
-{
-    if (e0 >= lo && e0 + 4 <= hi) {
-        *reinterpret_cast<float4*>(base + e0) = make_float4(vals[0], vals[1], vals[2], vals[3]);
-    } else {
-        for (int j = 0; j < 4; j++)
-            if (e0 + j >= lo && e0 + j < hi) base[e0 + j] = vals[j];
-    }
-}
 
 // zeros into the elements [lo, hi) of `base` (element 0 is 16-byte aligned), a quad per thread
 __device__ __forceinline__ void zero_range(float* base, long lo, long hi, int tid)
@@ -140,8 +102,8 @@ __global__ __launch_bounds__(UM_THREADS) void k_unmold_masks(const UnmoldParams 
         lo = fminf(lo, v);
         hi = fmaxf(hi, v);
     }
-    lo = wave_min(lo);
-    hi = wave_max(hi);
+    lo = wave_fminf(lo);
+    hi = wave_fmaxf(hi);
     if (lane == 0) {
         s_lo[wave] = lo;
         s_hi[wave] = hi;
@@ -197,7 +159,7 @@ __global__ __launch_bounds__(UM_THREADS) void k_unmold_masks(const UnmoldParams 
                 const int x0 = bh[2 * c], xc = bh[2 * c + 1];
                 int acc = 1 << (UM_BITS - 1);
                 for (int t = 0; t < xc; t++) acc += (int)src[min(x0 + t, A.Mw - 1)] * kh[c * o.ksize_h + t];
-                v = um_clip8(acc >> UM_BITS);
+                v = clip8(acc >> UM_BITS);
             } else {
                 v = src[c];
             }
@@ -229,7 +191,7 @@ __global__ __launch_bounds__(UM_THREADS) void k_unmold_masks(const UnmoldParams 
                     if (o.ksize_v) {
                         int acc = 1 << (UM_BITS - 1);
                         for (int t = 0; t < yc; t++) acc += (int)s_rows[min(max(y0 + t, 0), rows - 1) * cn + c] * kv[yo * o.ksize_v + t];
-                        v = um_clip8(acc >> UM_BITS);
+                        v = clip8(acc >> UM_BITS);
                     } else {
                         v = s_rows[min(max(y0, 0), rows - 1) * cn + c];
                     }

@@ -21,6 +21,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "device_common.h"
 #include "sdn_common.h"
 
 namespace sdn {
@@ -41,7 +42,6 @@ struct Paint2dRec {   // one row of the record table: (frame, object)
     int pad;
 };
 
-__device__ __forceinline__ int p2_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 
 // the highest set bit + 1 over the cover words of pixel p, 0 when none is set
 __device__ __forceinline__ int p2_top_bit(const uint32_t* __restrict__ cover, int chunks, size_t HW, size_t p)
@@ -104,14 +104,14 @@ __global__ __launch_bounds__(P2_THREADS) void k_scene_paint2d(const uint32_t* __
                     const int sx = r.c0 + min(max(x0 + s, 0), r.w - 1);
                     acc += (int)((row[sx] >> bit) & 1u) * 255 * kh[s];
                 }
-                hv = p2_clip8(acc >> P2_BITS);
+                hv = clip8(acc >> P2_BITS);
             } else {
                 hv = (int)((row[r.c0 + min(max(x0, 0), r.w - 1)] >> bit) & 1u) * 255;
             }
             if (kv) acc_v += hv * kv[t];
             else v = hv;
         }
-        if (kv) v = p2_clip8(acc_v >> P2_BITS);
+        if (kv) v = clip8(acc_v >> P2_BITS);
         // to_tensor, torch.round (:309-310): round((float32)v / 255) == 1.  127 / 255 = 0.498 and 128 / 255 = 0.50196, both far
         // from the tie at 0.5, so the test is v >= 128.
         if (v >= 128) {

@@ -17,6 +17,7 @@
 
 #include <cstdint>
 
+#include "device_common.h"
 #include "sdn_common.h"
 #include "segm_loss_check.h"
 
@@ -121,13 +122,6 @@ __device__ __forceinline__ void sgl_partial_group(const float* __restrict__ s0, 
     else lo[BHW] = s1 ? lse[0] : 0.f;
 }
 
-__device__ __forceinline__ int sgl_wave_sum(int v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 // CP: the class count rounded up to 8, 16 or 32 (register arrays); VEC: 16-byte loads of four adjacent pixels
 template <int CP, bool VEC>
 __global__ __launch_bounds__(SGL_THREADS) void k_segm_loss_partial(const float* __restrict__ s0, const float* __restrict__ s1,
@@ -152,9 +146,9 @@ __global__ __launch_bounds__(SGL_THREADS) void k_segm_loss_partial(const float* 
         a.s0 += __shfl_xor(a.s0, o, 64);
         a.s1 += __shfl_xor(a.s1, o, 64);
     }
-    a.hit = sgl_wave_sum(a.hit);
-    a.pix = sgl_wave_sum(a.pix);
-    a.bad = sgl_wave_sum(a.bad);
+    a.hit = wave_sum(a.hit);
+    a.pix = wave_sum(a.pix);
+    a.bad = wave_sum(a.bad);
     if (lane == 0) {
         psum[2 * (long)gb] = a.s0;
         psum[2 * (long)gb + 1] = a.s1;

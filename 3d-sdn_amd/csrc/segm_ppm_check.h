@@ -8,7 +8,7 @@
 #include <cstdint>
 #include <cstdio>
 
-#include "segm_tail_check.h"   // SEG_HD, SEG_FAIL
+#include "check_common.h"
 
 namespace sdn {
 
@@ -26,11 +26,11 @@ static_assert(PPM_TILE_ROWS * PPM_MAX_SIDE <= PPM_THREADS && PPM_THREADS / PPM_M
 static_assert(PPM_TILE_COLS % 4 == 0 && PPM_TILE_PITCH % 4 == 0, "16-byte tile rows");
 
 // nn.AdaptiveAvgPool2d's bin i of s over n positions: [floor(i n / s), ceil((i + 1) n / s))
-SEG_HD int ppm_bin_start(int i, int n, int s) { return (int)(((long)i * n) / s); }
-SEG_HD int ppm_bin_end(int i, int n, int s) { return (int)((((long)i + 1) * n + s - 1) / s); }
+SDN_HD int ppm_bin_start(int i, int n, int s) { return (int)(((long)i * n) / s); }
+SDN_HD int ppm_bin_end(int i, int n, int s) { return (int)((((long)i + 1) * n + s - 1) / s); }
 // the bins lo .. hi (inclusive) that cover position y: start(i) <= y  <=>  i n < (y + 1) s;  end(i) > y  <=>  (i + 1) n > y s.
 // For n >= s these are one or two bins; for n < s more (all s when n == 1).
-SEG_HD void ppm_cover(int y, int n, int s, int* lo, int* hi)
+SDN_HD void ppm_cover(int y, int n, int s, int* lo, int* hi)
 {
     *lo = (int)(((long)y * s) / n);
     long h = (((long)y + 1) * s - 1) / n;
@@ -39,7 +39,7 @@ SEG_HD void ppm_cover(int y, int n, int s, int* lo, int* hi)
 
 // bilinear taps of output position o of n over a map of s, align_corners=False, torch's fp32 rule (UpSample.h:
 // area_pixel_compute_source_index): scale = (float)s / n
-SEG_HD void ppm_taps(float scale, int o, int s, int* i0, int* i1, float* lam)
+SDN_HD void ppm_taps(float scale, int o, int s, int* i0, int* i1, float* lam)
 {
     float src = scale * ((float)o + 0.5f) - 0.5f;
     if (src < 0.f) src = 0.f;
@@ -50,7 +50,7 @@ SEG_HD void ppm_taps(float scale, int o, int s, int* i0, int* i1, float* lam)
     *lam = src - (float)a;
 }
 // the weight of output position o on tap j
-SEG_HD float ppm_tap_weight(float scale, int o, int s, int j)
+SDN_HD float ppm_tap_weight(float scale, int o, int s, int j)
 {
     int i0, i1;
     float lam;
@@ -59,7 +59,7 @@ SEG_HD float ppm_tap_weight(float scale, int o, int s, int j)
 }
 // a range [lo, hi) of output positions that holds every position with a weight on tap j: those whose source position lies in
 // [j - 1, j + 1), widened by a position either way against the rounding of the fp32 rule (tools/segm_ppm_check.cpp walks it)
-SEG_HD void ppm_tap_range(int j, int n, int s, int* lo, int* hi)
+SDN_HD void ppm_tap_range(int j, int n, int s, int* lo, int* hi)
 {
     const double r = (double)n / (double)s;
     long a = (long)(((double)j - 0.5) * r - 0.5) - 2;
@@ -100,29 +100,29 @@ inline void ppm_plan_make(const int* scales, const int* K, int S, PpmPlan* p)
 }
 
 // floats of the pooled buffer: p_k [B, C, s_k, s_k] one after the other; p_k begins at B * C * bb[k]
-SEG_HD long ppm_pooled_floats(int B, int C, int bins) { return (long)B * C * bins; }
-SEG_HD int ppm_chunks(long HW) { return (int)((HW + PPM_CHUNK - 1) / PPM_CHUNK); }   // workgroups per plane (fill, pool_bwd)
+SDN_HD long ppm_pooled_floats(int B, int C, int bins) { return (long)B * C * bins; }
+SDN_HD int ppm_chunks(long HW) { return (int)((HW + PPM_CHUNK - 1) / PPM_CHUNK); }   // workgroups per plane (fill, pool_bwd)
 // rows of a tile of k_ppm_pool: a thread per (row, column bin)
-SEG_HD int ppm_pool_rows(int colbins) { const int r = PPM_THREADS / colbins; return r < PPM_TILE_ROWS ? r : PPM_TILE_ROWS; }
+SDN_HD int ppm_pool_rows(int colbins) { const int r = PPM_THREADS / colbins; return r < PPM_TILE_ROWS ? r : PPM_TILE_ROWS; }
 
 // 0 when scales [S] (and K [S], unless NULL) and the sizes are valid; *ctot = C + sum K.  Otherwise 1 with the reason in msg
 inline int ppm_validate_sizes(const int* scales, const int* K, int S, int B, int C, int h, int w, int* ctot, char* msg, size_t cap)
 {
-    if (S < 1 || S > PPM_MAX_SCALES) SEG_FAIL("%d scales; 1 to %d are supported", S, PPM_MAX_SCALES);
-    if (!scales) SEG_FAIL("scales is NULL");
-    if (!K) SEG_FAIL("branch_channels is NULL");
-    if (B < 1 || C < 1 || h < 1 || w < 1) SEG_FAIL("bad sizes: B %d, C %d, h %d, w %d", B, C, h, w);
+    if (S < 1 || S > PPM_MAX_SCALES) SDN_FAIL("%d scales; 1 to %d are supported", S, PPM_MAX_SCALES);
+    if (!scales) SDN_FAIL("scales is NULL");
+    if (!K) SDN_FAIL("branch_channels is NULL");
+    if (B < 1 || C < 1 || h < 1 || w < 1) SDN_FAIL("bad sizes: B %d, C %d, h %d, w %d", B, C, h, w);
     long ct = C;
     for (int k = 0; k < S; k++) {
-        if (scales[k] < 1 || scales[k] > PPM_MAX_SIDE) SEG_FAIL("scale %d is %d; 1 to %d are supported", k, scales[k], PPM_MAX_SIDE);
-        if (K[k] < 1) SEG_FAIL("branch %d has %d channels", k, K[k]);
+        if (scales[k] < 1 || scales[k] > PPM_MAX_SIDE) SDN_FAIL("scale %d is %d; 1 to %d are supported", k, scales[k], PPM_MAX_SIDE);
+        if (K[k] < 1) SDN_FAIL("branch %d has %d channels", k, K[k]);
         ct += K[k];
-        if (ct > INT_MAX) SEG_FAIL("C + sum K must stay below 2^31");
+        if (ct > INT_MAX) SDN_FAIL("C + sum K must stay below 2^31");
     }
     // no product overflows: every factor is below 2^31 and the running product is checked before the next factor
     const long hw = (long)h * (long)w;
     if (hw > INT_MAX || hw * ct > INT_MAX || hw * ct * B > INT_MAX)
-        SEG_FAIL("B * Ctot * h * w = %d * %ld * %d * %d must stay below 2^31", B, ct, h, w);
+        SDN_FAIL("B * Ctot * h * w = %d * %ld * %d * %d must stay below 2^31", B, ct, h, w);
     *ctot = (int)ct;   // (the pooled buffer, B * C * sum s^2 floats, is indexed in 64 bits)
     return 0;
 }
@@ -130,10 +130,10 @@ inline int ppm_validate_sizes(const int* scales, const int* K, int S, int B, int
 inline int ppm_validate_pool(const void* conv5, const void* cat, const void* pooled, const int* scales, const int* K, int S, int B, int C,
                              int h, int w, int* ctot, char* msg, size_t cap)
 {
-    if (!conv5) SEG_FAIL("conv5 is NULL");
-    if (!cat || !pooled) SEG_FAIL("cat or pooled is NULL");
+    if (!conv5) SDN_FAIL("conv5 is NULL");
+    if (!cat || !pooled) SDN_FAIL("cat or pooled is NULL");
     if ((reinterpret_cast<uintptr_t>(conv5) | reinterpret_cast<uintptr_t>(cat) | reinterpret_cast<uintptr_t>(pooled)) & 3)
-        SEG_FAIL("conv5, cat and pooled must be aligned to 4 bytes");
+        SDN_FAIL("conv5, cat and pooled must be aligned to 4 bytes");
     return ppm_validate_sizes(scales, K, S, B, C, h, w, ctot, msg, cap);
 }
 
@@ -141,14 +141,14 @@ inline int ppm_validate_pool(const void* conv5, const void* cat, const void* poo
 inline int ppm_validate_fill(const float* const* y, const void* cat, const int* scales, const int* K, int S, int B, int C, int h, int w,
                              int* ctot, char* msg, size_t cap)
 {
-    if (!y) SEG_FAIL("y is NULL");
-    if (!cat) SEG_FAIL("cat is NULL");
+    if (!y) SDN_FAIL("y is NULL");
+    if (!cat) SDN_FAIL("cat is NULL");
     if (ppm_validate_sizes(scales, K, S, B, C, h, w, ctot, msg, cap)) return 1;
     for (int k = 0; k < S; k++) {
-        if (!y[k]) SEG_FAIL("y[%d] is NULL", k);
-        if (reinterpret_cast<uintptr_t>(y[k]) & 3) SEG_FAIL("y[%d] is not aligned to 4 bytes", k);
+        if (!y[k]) SDN_FAIL("y[%d] is NULL", k);
+        if (reinterpret_cast<uintptr_t>(y[k]) & 3) SDN_FAIL("y[%d] is not aligned to 4 bytes", k);
     }
-    if (reinterpret_cast<uintptr_t>(cat) & 3) SEG_FAIL("cat must be aligned to 4 bytes");
+    if (reinterpret_cast<uintptr_t>(cat) & 3) SDN_FAIL("cat must be aligned to 4 bytes");
     return 0;
 }
 
@@ -156,16 +156,16 @@ inline int ppm_validate_fill(const float* const* y, const void* cat, const int* 
 inline int ppm_validate_fill_bwd(const void* grad_cat, float* const* grad_y, const int* scales, const int* K, int S, int B, int C, int h,
                                  int w, int* ctot, char* msg, size_t cap)
 {
-    if (!grad_cat) SEG_FAIL("grad_cat is NULL");
-    if (!grad_y) SEG_FAIL("grad_y is NULL");
+    if (!grad_cat) SDN_FAIL("grad_cat is NULL");
+    if (!grad_y) SDN_FAIL("grad_y is NULL");
     if (ppm_validate_sizes(scales, K, S, B, C, h, w, ctot, msg, cap)) return 1;
     int asked = 0;
     for (int k = 0; k < S; k++) {
-        if (reinterpret_cast<uintptr_t>(grad_y[k]) & 3) SEG_FAIL("grad_y[%d] is not aligned to 4 bytes", k);
+        if (reinterpret_cast<uintptr_t>(grad_y[k]) & 3) SDN_FAIL("grad_y[%d] is not aligned to 4 bytes", k);
         asked += grad_y[k] ? 1 : 0;
     }
-    if (!asked) SEG_FAIL("no gradient asked for");
-    if (reinterpret_cast<uintptr_t>(grad_cat) & 3) SEG_FAIL("grad_cat must be aligned to 4 bytes");
+    if (!asked) SDN_FAIL("no gradient asked for");
+    if (reinterpret_cast<uintptr_t>(grad_cat) & 3) SDN_FAIL("grad_cat must be aligned to 4 bytes");
     return 0;
 }
 
@@ -173,16 +173,16 @@ inline int ppm_validate_fill_bwd(const void* grad_cat, float* const* grad_y, con
 inline int ppm_validate_pool_bwd(const void* grad_cat, const float* const* grad_p, const void* grad_conv5, const int* scales, const int* K,
                                  int S, int B, int C, int h, int w, int* ctot, char* msg, size_t cap)
 {
-    if (!grad_conv5) SEG_FAIL("grad_conv5 is NULL");
+    if (!grad_conv5) SDN_FAIL("grad_conv5 is NULL");
     if (ppm_validate_sizes(scales, K, S, B, C, h, w, ctot, msg, cap)) return 1;
     int given = grad_cat ? 1 : 0;
     for (int k = 0; k < S && grad_p; k++) {
-        if (reinterpret_cast<uintptr_t>(grad_p[k]) & 3) SEG_FAIL("grad_p[%d] is not aligned to 4 bytes", k);
+        if (reinterpret_cast<uintptr_t>(grad_p[k]) & 3) SDN_FAIL("grad_p[%d] is not aligned to 4 bytes", k);
         given += grad_p[k] ? 1 : 0;
     }
-    if (!given) SEG_FAIL("neither grad_cat nor any grad_p is given");
+    if (!given) SDN_FAIL("neither grad_cat nor any grad_p is given");
     if ((reinterpret_cast<uintptr_t>(grad_cat) | reinterpret_cast<uintptr_t>(grad_conv5)) & 3)
-        SEG_FAIL("grad_cat and grad_conv5 must be aligned to 4 bytes");
+        SDN_FAIL("grad_cat and grad_conv5 must be aligned to 4 bytes");
     return 0;
 }
 

@@ -21,6 +21,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "device_common.h"
 #include "sdn_common.h"
 #include "segm_tail_check.h"
 
@@ -126,12 +127,6 @@ __global__ __launch_bounds__(SEG_THREADS) void k_segm_fuse(const FuseParams A)
     }
 }
 
-__device__ __forceinline__ int seg_wave_sum(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
 // ---- ground-truth labels from colours ----------------------------------------------------------------------------------------
 constexpr int SEGC_THREADS = 256;
 
@@ -193,7 +188,7 @@ __global__ __launch_bounds__(SEGC_THREADS) void k_segm_colors(const uint8_t* __r
         const long wp1 = min(wp0 + 4 * 64, N) - 1;
         const long f0 = wp0 / HW;
         if (f0 == wp1 / HW) {
-            const int t = seg_wave_sum(miss);
+            const int t = wave_sum(miss);
             if (t && lane == 0) atomicAdd(unknown + f0, t);
         } else {
             for (int j = 0; j < have; j++)
@@ -248,9 +243,9 @@ __global__ __launch_bounds__(SEGF_THREADS) void k_segm_confusion(const uint8_t* 
         seg_wave_hist(row + C, pv, ok && pv < C, lane);
         seg_wave_hist(row + 2 * C, gv, ok && gv < C, lane);
     }
-    valid = seg_wave_sum(valid);
-    hit = seg_wave_sum(hit);
-    unk = seg_wave_sum(unk);
+    valid = wave_sum(valid);
+    hit = wave_sum(hit);
+    unk = wave_sum(unk);
     if (lane == 0) {
         row[3 * C] = hit;
         row[3 * C + 1] = valid;

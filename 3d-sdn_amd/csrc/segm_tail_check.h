@@ -7,11 +7,7 @@
 #include <cstdio>
 #include <cstring>
 
-#if defined(__HIPCC__)
-#define SEG_HD __host__ __device__ __forceinline__
-#else
-#define SEG_HD inline
-#endif
+#include "check_common.h"
 
 namespace sdn {
 
@@ -47,8 +43,8 @@ static_assert(sizeof(SegScale) == 4 * sizeof(int32_t), "scale table row");
 // nn.functional.upsample(mode='bilinear') as semantic/models.py:401 calls it (align_corners=False, torch 0.4's default): the
 // source position max(0, (dst + 0.5) * (in / out) - 0.5) with a float quotient; the taps i0, i1 and the weight l1 of the second
 // (the first weighs 1 - l1)
-SEG_HD float seg_scale(int in, int out) { return (float)in / (float)out; }
-SEG_HD void seg_taps(float scale, int dst, int in, int* i0, int* i1, float* l1)
+SDN_HD float seg_scale(int in, int out) { return (float)in / (float)out; }
+SDN_HD void seg_taps(float scale, int dst, int in, int* i0, int* i1, float* l1)
 {
     float src = scale * ((float)dst + 0.5f) - 0.5f;
     if (src < 0.f) src = 0.f;
@@ -60,7 +56,7 @@ SEG_HD void seg_taps(float scale, int dst, int in, int* i0, int* i1, float* l1)
 }
 
 // first source row (column) and number of rows of the outputs d0 .. d1 (inclusive), clamped to `cap` rows
-SEG_HD void seg_footprint(float scale, int d0, int d1, int in, int cap, int* first, int* count)
+SDN_HD void seg_footprint(float scale, int d0, int d1, int in, int cap, int* first, int* count)
 {
     int a0, a1, b0, b1;
     float l;
@@ -73,27 +69,21 @@ SEG_HD void seg_footprint(float scale, int d0, int d1, int in, int cap, int* fir
     *count = n;
 }
 
-#define SEG_FAIL(...)                         \
-    do {                                      \
-        std::snprintf(msg, cap, __VA_ARGS__); \
-        return 1;                             \
-    } while (0)
-
 // 0 when the HOST table of sdn_segm_fuse is valid; otherwise 1 with the reason in msg
 inline int seg_validate_fuse(const int32_t* table, int S, int B, int C, int H, int W, char* msg, size_t cap)
 {
-    if (S < 1 || S > SEG_MAX_SCALES) SEG_FAIL("%d scales; 1 to %d are supported", S, SEG_MAX_SCALES);
-    if (C < 1 || C > SEG_MAX_CLASSES) SEG_FAIL("%d classes; 1 to %d are supported", C, SEG_MAX_CLASSES);
-    if (B < 1 || B > 65535) SEG_FAIL("%d frames; 1 to 65535 are supported", B);
-    if (H < 1 || W < 1 || H > SEG_MAX_SIDE || W > SEG_MAX_SIDE) SEG_FAIL("bad sizes: a %d x %d label map", H, W);
+    if (S < 1 || S > SEG_MAX_SCALES) SDN_FAIL("%d scales; 1 to %d are supported", S, SEG_MAX_SCALES);
+    if (C < 1 || C > SEG_MAX_CLASSES) SDN_FAIL("%d classes; 1 to %d are supported", C, SEG_MAX_CLASSES);
+    if (B < 1 || B > 65535) SDN_FAIL("%d frames; 1 to 65535 are supported", B);
+    if (H < 1 || W < 1 || H > SEG_MAX_SIDE || W > SEG_MAX_SIDE) SDN_FAIL("bad sizes: a %d x %d label map", H, W);
     for (int s = 0; s < S; s++) {
         SegScale r;
         std::memcpy(&r, table + 4 * (size_t)s, sizeof(r));
-        if (!r.scores) SEG_FAIL("scale %d: null address", s);
-        if (r.scores & 3) SEG_FAIL("scale %d: the map is not aligned to 4 bytes", s);
-        if (r.h < 1 || r.w < 1 || r.h > SEG_MAX_SIDE || r.w > SEG_MAX_SIDE) SEG_FAIL("scale %d: bad sizes: a %d x %d map", s, r.h, r.w);
+        if (!r.scores) SDN_FAIL("scale %d: null address", s);
+        if (r.scores & 3) SDN_FAIL("scale %d: the map is not aligned to 4 bytes", s);
+        if (r.h < 1 || r.w < 1 || r.h > SEG_MAX_SIDE || r.w > SEG_MAX_SIDE) SDN_FAIL("scale %d: bad sizes: a %d x %d map", s, r.h, r.w);
         if (r.h > 2 * H || r.w > 2 * W)
-            SEG_FAIL("scale %d: a %d x %d map for a %d x %d output; a map may be at most twice the output", s, r.h, r.w, H, W);
+            SDN_FAIL("scale %d: a %d x %d map for a %d x %d output; a map may be at most twice the output", s, r.h, r.w, H, W);
     }
     return 0;
 }
@@ -101,18 +91,18 @@ inline int seg_validate_fuse(const int32_t* table, int S, int B, int C, int H, i
 // 0 when the HOST colour table (codes [K] ascending, then labels [K]) of sdn_segm_labels_from_colors is valid
 inline int seg_validate_colors(const int32_t* table, int K, char* msg, size_t cap)
 {
-    if (K < 1 || K > SEG_MAX_COLORS) SEG_FAIL("%d colour codes; 1 to %d are supported", K, SEG_MAX_COLORS);
+    if (K < 1 || K > SEG_MAX_COLORS) SDN_FAIL("%d colour codes; 1 to %d are supported", K, SEG_MAX_COLORS);
     for (int k = 0; k < K; k++) {
-        if (table[k] < 0 || table[k] > 0xffffff) SEG_FAIL("code %d is 0x%x; a code is r | g << 8 | b << 16", k, (unsigned)table[k]);
-        if (k && table[k] <= table[k - 1]) SEG_FAIL("code %d: the codes are not sorted in strictly ascending order", k);
+        if (table[k] < 0 || table[k] > 0xffffff) SDN_FAIL("code %d is 0x%x; a code is r | g << 8 | b << 16", k, (unsigned)table[k]);
+        if (k && table[k] <= table[k - 1]) SDN_FAIL("code %d: the codes are not sorted in strictly ascending order", k);
         // vkitti_dataset.py:209 stores the label in a uint8
-        if (table[K + k] < 0 || table[K + k] > 255) SEG_FAIL("code %d: label %d outside 0 .. 255", k, table[K + k]);
+        if (table[K + k] < 0 || table[K + k] > 255) SDN_FAIL("code %d: label %d outside 0 .. 255", k, table[K + k]);
     }
     return 0;
 }
 
 // index of `code` in the ascending codes [K], or -1
-SEG_HD int seg_find(const int32_t* codes, int K, int code)
+SDN_HD int seg_find(const int32_t* codes, int K, int code)
 {
     int lo = 0, hi = K;   // the answer, if any, lies in [lo, hi)
     while (hi - lo > 1) {

@@ -73,7 +73,7 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_luma(const SegTrainP
         ti_jitter(ji, at, 0, r, g, bl);
         acc += ti_luma(r, g, bl);
     }
-    acc = ti_wave_sum(acc);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) s_part[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_image(const SegTrain
         if (ti_contrast_at(ji) >= 0) {   // int(mean(L) + 0.5) = (2 sum + n) / (2 n) in integers; the sum is below 2^21 * 255
             int acc = 0;
             for (int i = tid; i < A.nblk; i += SGT_THREADS) acc += A.partial[(size_t)b * A.nblk + i];
-            acc = ti_wave_sum(acc);
+            acc = wave_sum(acc);
             if ((tid & 63) == 0) s_part[tid >> 6] = acc;
             __syncthreads();
             long long sum = 0;
@@ -241,7 +241,7 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_labels(const SegTrai
         }
         A.labels[(size_t)b * Hl * Wl + i] = (long long)lab;
     }
-    miss = ti_wave_sum(miss);   // every wave of the workgroup gets here
+    miss = wave_sum(miss);   // every wave of the workgroup gets here
     if (miss && (tid & 63) == 0) atomicAdd(A.unknown + b, miss);
 }
 

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstring>
 
+#include "check_common.h"
 #include "segm_tail_check.h"   // the colour table: SEG_MAX_COLORS, seg_validate_colors, seg_find
 
 namespace sdn {
@@ -70,27 +71,21 @@ inline void sgt_band_span(const int32_t* bounds, int r0, int r1, int* first, int
     *count = hi - lo;
 }
 
-#define SGT_FAIL(...)                         \
-    do {                                      \
-        std::snprintf(msg, cap, __VA_ARGS__); \
-        return 1;                             \
-    } while (0)
-
 // one resampling table of an item: its place in the buffer and every entry
 inline int sgt_validate_axis(const int32_t* T, long n, long first_free, int item, const char* axis, int in, int out, int boff, int koff,
                              int ksize, char* msg, size_t cap)
 {
     if (in == out) {
-        if (ksize != 0) SGT_FAIL("item %d: a table for the %s resize %d -> %d, which Pillow skips", item, axis, in, out);
+        if (ksize != 0) SDN_FAIL("item %d: a table for the %s resize %d -> %d, which Pillow skips", item, axis, in, out);
         return 0;
     }
-    if (ksize != sgt_taps(in, out)) SGT_FAIL("item %d: %d taps for the %s resize %d -> %d, Pillow uses %d", item, ksize, axis, in, out, sgt_taps(in, out));
+    if (ksize != sgt_taps(in, out)) SDN_FAIL("item %d: %d taps for the %s resize %d -> %d, Pillow uses %d", item, ksize, axis, in, out, sgt_taps(in, out));
     if (boff < first_free || koff < first_free || (long)boff + 2L * out > n || (long)koff + (long)out * ksize > n)
-        SGT_FAIL("item %d: the %s tables (%d, %d) of %d -> %d lie outside the buffer of %ld ints", item, axis, boff, koff, in, out, n);
+        SDN_FAIL("item %d: the %s tables (%d, %d) of %d -> %d lie outside the buffer of %ld ints", item, axis, boff, koff, in, out, n);
     for (int i = 0; i < out; i++) {
         const int a = T[boff + 2 * i], c = T[boff + 2 * i + 1];
         if (a < 0 || c < 1 || c > ksize || (long)a + c > in)
-            SGT_FAIL("item %d: %s bounds of output %d are (%d, %d) for %d inputs and %d taps", item, axis, i, a, c, in, ksize);
+            SDN_FAIL("item %d: %s bounds of output %d are (%d, %d) for %d inputs and %d taps", item, axis, i, a, c, in, ksize);
     }
     return 0;
 }
@@ -98,30 +93,30 @@ inline int sgt_validate_axis(const int32_t* T, long n, long first_free, int item
 // 0 when the HOST copy of the table buffer of sdn_segm_train_batch is valid and fits the LDS plan; otherwise 1 with the reason
 inline int sgt_validate(const int32_t* T, long n, int B, int H, int W, int Hb, int Wb, int rate, char* msg, size_t cap)
 {
-    if (B < 1 || B > 65535) SGT_FAIL("%d items; 1 to 65535 are supported", B);
-    if (H < 1 || W < 1 || (long)H * W > INT_MAX / 4 || (long)B * H * W > INT_MAX / 3) SGT_FAIL("bad sizes: %d frames of %d x %d", B, H, W);
-    if (W > SGT_SRC_PIXELS) SGT_FAIL("frames %d pixels wide: one frame row must fit the %d pixel staging tile", W, SGT_SRC_PIXELS);
-    if (Hb < 1 || Wb < 1 || Hb > SGT_MAX_SIDE || Wb > SGT_MAX_SIDE) SGT_FAIL("bad sizes: a %d x %d batch", Hb, Wb);
-    if (rate < 1 || rate > Hb || rate > Wb) SGT_FAIL("label rate %d for a %d x %d batch", rate, Hb, Wb);
+    if (B < 1 || B > 65535) SDN_FAIL("%d items; 1 to 65535 are supported", B);
+    if (H < 1 || W < 1 || (long)H * W > INT_MAX / 4 || (long)B * H * W > INT_MAX / 3) SDN_FAIL("bad sizes: %d frames of %d x %d", B, H, W);
+    if (W > SGT_SRC_PIXELS) SDN_FAIL("frames %d pixels wide: one frame row must fit the %d pixel staging tile", W, SGT_SRC_PIXELS);
+    if (Hb < 1 || Wb < 1 || Hb > SGT_MAX_SIDE || Wb > SGT_MAX_SIDE) SDN_FAIL("bad sizes: a %d x %d batch", Hb, Wb);
+    if (rate < 1 || rate > Hb || rate > Wb) SDN_FAIL("label rate %d for a %d x %d batch", rate, Hb, Wb);
     const long first_free = (long)B * SGT_ITEM_INTS;
-    if (n < first_free) SGT_FAIL("a buffer of %ld ints cannot hold %d item rows", n, B);
+    if (n < first_free) SDN_FAIL("a buffer of %ld ints cannot hold %d item rows", n, B);
     for (int i = 0; i < B; i++) {
         SegTrainItem it;
         std::memcpy(&it, T + (size_t)i * SGT_ITEM_INTS, sizeof(it));
-        if (it.h < 1 || it.w < 1 || it.h > Hb || it.w > Wb) SGT_FAIL("item %d: resized to %d x %d in a %d x %d batch", i, it.h, it.w, Hb, Wb);
+        if (it.h < 1 || it.w < 1 || it.h > Hb || it.w > Wb) SDN_FAIL("item %d: resized to %d x %d in a %d x %d batch", i, it.h, it.w, Hb, Wb);
         if ((it.h + rate - 1) / rate > Hb / rate || (it.w + rate - 1) / rate > Wb / rate)
-            SGT_FAIL("item %d: the labels of %d x %d at rate %d do not fit the %d x %d map (the reference fails there too)", i, it.h, it.w,
+            SDN_FAIL("item %d: the labels of %d x %d at rate %d do not fit the %d x %d map (the reference fails there too)", i, it.h, it.w,
                      rate, Hb / rate, Wb / rate);
-        if (it.flip != 0 && it.flip != 1) SGT_FAIL("item %d: flip %d", i, it.flip);
-        if (it.nops < 0 || it.nops > 4 || it.hue < 0 || it.hue > 255) SGT_FAIL("item %d: %d ops, hue shift %d", i, it.nops, it.hue);
+        if (it.flip != 0 && it.flip != 1) SDN_FAIL("item %d: flip %d", i, it.flip);
+        if (it.nops < 0 || it.nops > 4 || it.hue < 0 || it.hue > 255) SDN_FAIL("item %d: %d ops, hue shift %d", i, it.nops, it.hue);
         int seen = 0;
         for (int k = 0; k < it.nops; k++) {
             const int op = (it.order >> (4 * k)) & 15;
-            if (op > 3 || (seen >> op) & 1) SGT_FAIL("item %d: order 0x%x is not a permutation of distinct ops", i, it.order);
+            if (op > 3 || (seen >> op) & 1) SDN_FAIL("item %d: order 0x%x is not a permutation of distinct ops", i, it.order);
             seen |= 1 << op;
         }
         if (((seen >> 1) & 1) && (long)H * W > SGT_MAX_CONTRAST_PIXELS)
-            SGT_FAIL("item %d: contrast on a frame of %ld pixels (at most %ld)", i, (long)H * W, SGT_MAX_CONTRAST_PIXELS);
+            SDN_FAIL("item %d: contrast on a frame of %ld pixels (at most %ld)", i, (long)H * W, SGT_MAX_CONTRAST_PIXELS);
         if (sgt_validate_axis(T, n, first_free, i, "horizontal", W, it.w, it.xb, it.xk, it.xksize, msg, cap)) return 1;
         if (sgt_validate_axis(T, n, first_free, i, "vertical", H, it.h, it.yb, it.yk, it.yksize, msg, cap)) return 1;
         // the LDS plan: every band's resampled source rows in one plane
@@ -131,19 +126,19 @@ inline int sgt_validate(const int32_t* T, long n, int B, int H, int W, int Hb, i
             int first, count;
             sgt_band_span(it.yksize ? T + it.yb : nullptr, r0, r1, &first, &count);
             if (count > rows_cap)
-                SGT_FAIL("item %d: %d x %d -> %d x %d does not fit the LDS plan: the output rows %d .. %d need %d source rows of %d "
+                SDN_FAIL("item %d: %d x %d -> %d x %d does not fit the LDS plan: the output rows %d .. %d need %d source rows of %d "
                          "bytes, a plane holds %d", i, H, W, it.h, it.w, r0, r1 - 1, count, it.w, rows_cap);
         }
         if (it.xn < first_free || it.yn < first_free || (long)it.xn + it.w > n || (long)it.yn + it.h > n)
-            SGT_FAIL("item %d: the NEAREST tables (%d, %d) lie outside the buffer of %ld ints", i, it.xn, it.yn, n);
+            SDN_FAIL("item %d: the NEAREST tables (%d, %d) lie outside the buffer of %ld ints", i, it.xn, it.yn, n);
         for (int x = 0; x < it.w; x++)
-            if (T[it.xn + x] < 0 || T[it.xn + x] >= W) SGT_FAIL("item %d: NEAREST column %d reads column %d of %d", i, x, T[it.xn + x], W);
+            if (T[it.xn + x] < 0 || T[it.xn + x] >= W) SDN_FAIL("item %d: NEAREST column %d reads column %d of %d", i, x, T[it.xn + x], W);
         for (int y = 0; y < it.h; y++)
-            if (T[it.yn + y] < 0 || T[it.yn + y] >= H) SGT_FAIL("item %d: NEAREST row %d reads row %d of %d", i, y, T[it.yn + y], H);
-        if (it.K < 1 || it.K > SEG_MAX_COLORS) SGT_FAIL("item %d: %d colour codes; 1 to %d are supported", i, it.K, SEG_MAX_COLORS);
-        if (it.ct < first_free || (long)it.ct + 2L * it.K > n) SGT_FAIL("item %d: the colour table at %d lies outside the buffer of %ld ints", i, it.ct, n);
+            if (T[it.yn + y] < 0 || T[it.yn + y] >= H) SDN_FAIL("item %d: NEAREST row %d reads row %d of %d", i, y, T[it.yn + y], H);
+        if (it.K < 1 || it.K > SEG_MAX_COLORS) SDN_FAIL("item %d: %d colour codes; 1 to %d are supported", i, it.K, SEG_MAX_COLORS);
+        if (it.ct < first_free || (long)it.ct + 2L * it.K > n) SDN_FAIL("item %d: the colour table at %d lies outside the buffer of %ld ints", i, it.ct, n);
         char why[160];
-        if (seg_validate_colors(T + it.ct, it.K, why, sizeof(why))) SGT_FAIL("item %d: %s", i, why);
+        if (seg_validate_colors(T + it.ct, it.K, why, sizeof(why))) SDN_FAIL("item %d: %s", i, why);
     }
     return 0;
 }

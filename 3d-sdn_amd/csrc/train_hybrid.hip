@@ -114,9 +114,9 @@ __global__ __launch_bounds__(TID_THREADS) void k_tid_pass_a(const IdItem* __rest
             }
         }
     }
-    area = ti_wave_sum(area);
-    n = ti_wave_sum(n);
-    ymin = ti_wave_min(ymin); xmin = ti_wave_min(xmin); ymax = ti_wave_max(ymax); xmax = ti_wave_max(xmax);
+    area = wave_sum(area);
+    n = wave_sum(n);
+    ymin = wave_imin(ymin); xmin = wave_imin(xmin); ymax = wave_imax(ymax); xmax = wave_imax(xmax);
     if (lane == 0 && area) {
         atomicAdd(&s_stat[0], area);
         atomicMin(&s_stat[1], ymin);

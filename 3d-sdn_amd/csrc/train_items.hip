@@ -120,9 +120,9 @@ __global__ __launch_bounds__(TI_THREADS) void k_train_rois(const uint8_t* __rest
         ymin = min(ymin, y); xmin = min(xmin, x); ymax = max(ymax, y); xmax = max(xmax, x);
         cnt++;
     }
-    cnt = ti_wave_sum(cnt);
+    cnt = wave_sum(cnt);
     if (cnt) {   // uniform over the wave
-        ymin = ti_wave_min(ymin); xmin = ti_wave_min(xmin); ymax = ti_wave_max(ymax); xmax = ti_wave_max(xmax);
+        ymin = wave_imin(ymin); xmin = wave_imin(xmin); ymax = wave_imax(ymax); xmax = wave_imax(xmax);
         if ((threadIdx.x & 63) == 0) {
             atomicMin(table + 5 * b, ymin);
             atomicMin(table + 5 * b + 1, xmin);

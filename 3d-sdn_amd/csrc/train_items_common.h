@@ -7,6 +7,8 @@
 
 #include <cstdint>
 
+#include "device_common.h"
+
 namespace sdn {
 
 constexpr int TI_BITS = 22;             // Pillow Resample.c: PRECISION_BITS = 32 - 8 - 2
@@ -47,31 +49,13 @@ struct TrainItem {  // one row of the item table
     int pad0, pad1;
 };
 
-__device__ __forceinline__ int ti_clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
 // One byte of a pass of Pillow's ImagingResample over 8-bit data (22-bit fixed point, rounded and clipped as Pillow stores it): the
 // taps first .. first + count of the bytes p[i * stride], the index held inside [0, last].
 __device__ __forceinline__ int ti_resample_byte(const uint8_t* p, int stride, int first, int count, int last, const int32_t* k)
 {
     int acc = 1 << (TI_BITS - 1);
     for (int t = 0; t < count; t++) acc += (int)p[min(max(first + t, 0), last) * stride] * k[t];
-    return ti_clip8(acc >> TI_BITS);
-}
-
-__device__ __forceinline__ int ti_wave_sum(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-__device__ __forceinline__ int ti_wave_min(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = min(v, __shfl_xor(v, d, 64));
-    return v;
-}
-__device__ __forceinline__ int ti_wave_max(int v)
-{
-    for (int d = 32; d > 0; d >>= 1) v = max(v, __shfl_xor(v, d, 64));
-    return v;
+    return clip8(acc >> TI_BITS);
 }
 
 // ---- Pillow's arithmetic ---------------------------------------------------------------------------------------------------
@@ -109,8 +93,8 @@ __device__ __forceinline__ void ti_hue(int shift, int& r, int& g, int& b)
         double t = (double)h / 6.0 + 1.0;
         if (t >= 1.0) t = t - 1.0;   // fmod(t, 1.0) for t in [5/6, 11/6]
         h = (float)t;
-        uh = ti_clip8((int)((double)h * 255.0));
-        us = ti_clip8((int)((double)s * 255.0));
+        uh = clip8((int)((double)h * 255.0));
+        us = clip8((int)((double)s * 255.0));
     }
     uh = (uh + shift) & 255;
     if (us == 0) {
@@ -122,9 +106,9 @@ __device__ __forceinline__ void ti_hue(int shift, int& r, int& g, int& b)
     const float f = (float)(h6 - (double)(float)i);
     const float fs = (float)((double)(float)us / 255.0);
     const double v = (double)(float)uv;
-    const int p = ti_clip8(ti_round(v * (1.0 - (double)fs)));
-    const int q = ti_clip8(ti_round(v * (1.0 - (double)(fs * f))));
-    const int t = ti_clip8(ti_round(v * (1.0 - (double)fs * (1.0 - (double)f))));
+    const int p = clip8(ti_round(v * (1.0 - (double)fs)));
+    const int q = clip8(ti_round(v * (1.0 - (double)(fs * f))));
+    const int t = clip8(ti_round(v * (1.0 - (double)fs * (1.0 - (double)f))));
     switch (i % 6) {
         case 0: r = uv; g = t; b = p; break;
         case 1: r = q; g = uv; b = p; break;
@@ -188,7 +172,7 @@ __device__ __forceinline__ void ti_stats_body(const Src& src, const TrainWin& o,
         ti_jitter(it, at, 0, r, g, b);
         acc += ti_luma(r, g, b);
     }
-    acc = ti_wave_sum(acc);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) s_part[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -272,7 +256,7 @@ __device__ __forceinline__ void ti_crops_body(const Src& src, const TrainWin& o,
                 const uint8_t* row = s_src + ch * TI_SRC_PIXELS + ry * s;
                 int acc = 1 << (TI_BITS - 1);
                 for (int t = 0; t < xc; t++) acc += (int)row[min(x0 + t, s - 1)] * k[x * ksize + t];
-                s_rows[ch * TI_PLANE_BYTES + (c0 + ry) * S + x] = (uint8_t)ti_clip8(acc >> TI_BITS);
+                s_rows[ch * TI_PLANE_BYTES + (c0 + ry) * S + x] = (uint8_t)clip8(acc >> TI_BITS);
             }
             __syncthreads();
         }
@@ -284,7 +268,7 @@ __device__ __forceinline__ void ti_crops_body(const Src& src, const TrainWin& o,
             const uint8_t* plane = s_rows + ch * TI_PLANE_BYTES;
             int acc = 1 << (TI_BITS - 1);
             for (int t = 0; t < yc; t++) acc += (int)plane[min(max(y0 + t, 0), rows - 1) * S + x] * k[y * ksize + t];
-            float v = (float)ti_clip8(acc >> TI_BITS) / 255.f;
+            float v = (float)clip8(acc >> TI_BITS) / 255.f;
             if (img) v = (v - src.mean(ch)) / src.stdev(ch);
             out[((size_t)ch * S + y) * S + x] = v;
         }

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(TRI_THREADS) void k_tri_luma(const TriArgs A)
         ti_jitter(ji, at, 0, r, g, bl);
         acc += ti_luma(r, g, bl);
     }
-    acc = ti_wave_sum(acc);
+    acc = wave_sum(acc);
     if ((tid & 63) == 0) s_part[tid >> 6] = acc;
     __syncthreads();
     if (tid == 0) {
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(TRI_THREADS) void k_tri_image(const TriArgs A)
         if (ti_contrast_at(ji) >= 0) {   // int(mean(L) + 0.5) = (2 sum + n) / (2 n) in integers; the sum is below 2^21 * 255
             int acc = 0;
             for (int i = tid; i < A.nblk; i += TRI_THREADS) acc += A.partial[(size_t)b * A.nblk + i];
-            acc = ti_wave_sum(acc);
+            acc = wave_sum(acc);
             if ((tid & 63) == 0) s_part[tid >> 6] = acc;
             __syncthreads();
             long long sum = 0;

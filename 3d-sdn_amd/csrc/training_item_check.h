@@ -6,7 +6,7 @@
 #include <cmath>
 #include <cstring>
 
-#include "detection_targets_check.h"
+#include "detection_targets_check.h"   // DT_MAX_BOXES, PROP_ALIGN
 #include "segm_train_check.h"
 
 namespace sdn {
@@ -47,21 +47,21 @@ static_assert(sizeof(TriPlan) == TRI_PLAN_INTS * sizeof(int32_t), "parameter blo
 
 // ---- Pillow's precompute_coeffs and normalize_coeffs_8bpc for the bilinear filter (Resample.c), the box being the whole image:
 // operation for operation sdn_hip/pillow.py's resample_tables and fixed_point.  Only + - * /, ceil and truncation occur.
-PROP_HD double tri_scale(int in, int out) { return (double)((float)in - 0.0f) / (double)out; }
-PROP_HD int tri_ksize(int in, int out)
+SDN_HD double tri_scale(int in, int out) { return (double)((float)in - 0.0f) / (double)out; }
+SDN_HD int tri_ksize(int in, int out)
 {
     const double scale = tri_scale(in, out);
     const double support = 1.0 * (scale < 1.0 ? 1.0 : scale);
     return (int)ceil(support) * 2 + 1;
 }
-PROP_HD double tri_weight(int x, int xmin, double center, double ss)
+SDN_HD double tri_weight(int x, int xmin, double center, double ss)
 {
     double arg = ((double)(x + xmin) - center + 0.5) * ss;
     if (arg < 0.0) arg = -arg;
     return arg < 1.0 ? 1.0 - arg : 0.0;
 }
 // output xx of the resize in -> out: the first source index, the number of taps and the ksize fixed-point coefficients
-PROP_HD void tri_coeffs(int in, int out, int xx, int ksize, int* first, int* count, int32_t* k)
+SDN_HD void tri_coeffs(int in, int out, int xx, int ksize, int* first, int* count, int32_t* k)
 {
     const double scale = tri_scale(in, out);
     const double filterscale = scale < 1.0 ? 1.0 : scale;
@@ -94,23 +94,23 @@ struct TriLayout {
 
 inline int tri_validate_sizes(int B, int H, int W, int G, char* msg, size_t cap)
 {
-    if (B < 1 || B > TRI_MAX_FRAMES) PROP_FAIL("%d frames; 1 to %d of one size are supported", B, TRI_MAX_FRAMES);
-    if (H < 1 || W < 1 || (long)H * W > INT_MAX / 4 || (long)B * H * W > INT_MAX / 3) PROP_FAIL("bad sizes: %d frames of %d x %d", B, H, W);
-    if (W > SGT_SRC_PIXELS) PROP_FAIL("frames %d pixels wide: one frame row must fit the %d pixel staging tile", W, SGT_SRC_PIXELS);
-    if (G < 0 || G > TRI_MAX_BOXES) PROP_FAIL("G %d; 1 to %d instances are supported", G, TRI_MAX_BOXES);
+    if (B < 1 || B > TRI_MAX_FRAMES) SDN_FAIL("%d frames; 1 to %d of one size are supported", B, TRI_MAX_FRAMES);
+    if (H < 1 || W < 1 || (long)H * W > INT_MAX / 4 || (long)B * H * W > INT_MAX / 3) SDN_FAIL("bad sizes: %d frames of %d x %d", B, H, W);
+    if (W > SGT_SRC_PIXELS) SDN_FAIL("frames %d pixels wide: one frame row must fit the %d pixel staging tile", W, SGT_SRC_PIXELS);
+    if (G < 0 || G > TRI_MAX_BOXES) SDN_FAIL("G %d; 1 to %d instances are supported", G, TRI_MAX_BOXES);
     return 0;
 }
 
 inline int tri_layout(int B, int H, int W, int G, TriLayout* L, char* msg, size_t cap)
 {
     if (tri_validate_sizes(B, H, W, G, msg, cap)) return 1;
-    if (!L) PROP_FAIL("the layout is NULL");
+    if (!L) SDN_FAIL("the layout is NULL");
     const size_t nblk = (size_t)(((long)H * W + SGT_STAT_PIXELS - 1) / SGT_STAT_PIXELS);
     size_t at = 0;
     L->partial = at;
-    at += prop_round(sizeof(int32_t) * (size_t)B * nblk);
+    at += round_up(sizeof(int32_t) * (size_t)B * nblk, PROP_ALIGN);
     L->acc = at;
-    at += prop_round(sizeof(int32_t) * (size_t)TRI_ACC_ROWS * (size_t)(G > 0 ? G : 1));
+    at += round_up(sizeof(int32_t) * (size_t)TRI_ACC_ROWS * (size_t)(G > 0 ? G : 1), PROP_ALIGN);
     L->total = at;
     return 0;
 }
@@ -118,25 +118,25 @@ inline int tri_layout(int B, int H, int W, int G, TriLayout* L, char* msg, size_
 // 0 when the HOST copy of the parameter block is valid for frames of H x W and fits the LDS plan; otherwise 1 with the reason
 inline int tri_validate_plan(const int32_t* T, long n, int H, int W, char* msg, size_t cap)
 {
-    if (!T) PROP_FAIL("the host copy of the parameter block is NULL");
-    if (n < TRI_PLAN_INTS) PROP_FAIL("a parameter block of %ld ints cannot hold its head of %d", n, TRI_PLAN_INTS);
+    if (!T) SDN_FAIL("the host copy of the parameter block is NULL");
+    if (n < TRI_PLAN_INTS) SDN_FAIL("a parameter block of %ld ints cannot hold its head of %d", n, TRI_PLAN_INTS);
     TriPlan p;
     std::memcpy(&p, T, sizeof(p));
-    if (p.H != H || p.W != W) PROP_FAIL("the plan is for frames of %d x %d, the frames are %d x %d", p.H, p.W, H, W);
-    if (p.M < 1 || p.M > TRI_MAX_DIM) PROP_FAIL("IMAGE_MAX_DIM %d; 1 to %d is supported", p.M, TRI_MAX_DIM);
-    if (p.oh < 1 || p.ow < 1 || p.oh > p.M || p.ow > p.M) PROP_FAIL("resized to %d x %d in a %d x %d image", p.oh, p.ow, p.M, p.M);
+    if (p.H != H || p.W != W) SDN_FAIL("the plan is for frames of %d x %d, the frames are %d x %d", p.H, p.W, H, W);
+    if (p.M < 1 || p.M > TRI_MAX_DIM) SDN_FAIL("IMAGE_MAX_DIM %d; 1 to %d is supported", p.M, TRI_MAX_DIM);
+    if (p.oh < 1 || p.ow < 1 || p.oh > p.M || p.ow > p.M) SDN_FAIL("resized to %d x %d in a %d x %d image", p.oh, p.ow, p.M, p.M);
     if (p.top != (p.M - p.oh) / 2 || p.left != (p.M - p.ow) / 2)
-        PROP_FAIL("padding (%d, %d) before a %d x %d frame in a %d x %d image", p.top, p.left, p.oh, p.ow, p.M, p.M);
-    if (p.flip != 0 && p.flip != 1) PROP_FAIL("flip %d", p.flip);
-    if (p.nops < 0 || p.nops > 4 || p.hue < 0 || p.hue > 255) PROP_FAIL("%d ops, hue shift %d", p.nops, p.hue);
+        SDN_FAIL("padding (%d, %d) before a %d x %d frame in a %d x %d image", p.top, p.left, p.oh, p.ow, p.M, p.M);
+    if (p.flip != 0 && p.flip != 1) SDN_FAIL("flip %d", p.flip);
+    if (p.nops < 0 || p.nops > 4 || p.hue < 0 || p.hue > 255) SDN_FAIL("%d ops, hue shift %d", p.nops, p.hue);
     int seen = 0;
     for (int k = 0; k < p.nops; k++) {
         const int op = (p.order >> (4 * k)) & 15;
-        if (op > 3 || (seen >> op) & 1) PROP_FAIL("order 0x%x is not a permutation of distinct ops", p.order);
+        if (op > 3 || (seen >> op) & 1) SDN_FAIL("order 0x%x is not a permutation of distinct ops", p.order);
         seen |= 1 << op;
     }
     if (((seen >> 1) & 1) && (long)H * W > SGT_MAX_CONTRAST_PIXELS)
-        PROP_FAIL("contrast on a frame of %ld pixels (at most %ld)", (long)H * W, SGT_MAX_CONTRAST_PIXELS);
+        SDN_FAIL("contrast on a frame of %ld pixels (at most %ld)", (long)H * W, SGT_MAX_CONTRAST_PIXELS);
     if (sgt_validate_axis(T, n, TRI_PLAN_INTS, 0, "horizontal", W, p.ow, p.xb, p.xk, p.xksize, msg, cap)) return 1;
     if (sgt_validate_axis(T, n, TRI_PLAN_INTS, 0, "vertical", H, p.oh, p.yb, p.yk, p.yksize, msg, cap)) return 1;
     const int rows_cap = SGT_PLANE_BYTES / p.ow;
@@ -147,16 +147,16 @@ inline int tri_validate_plan(const int32_t* T, long n, int H, int W, char* msg, 
         int first, count;
         sgt_band_span(p.yksize ? T + p.yb : nullptr, r0, r1, &first, &count);
         if (count > rows_cap)
-            PROP_FAIL("%d x %d -> %d x %d does not fit the LDS plan: the output rows %d .. %d need %d source rows of %d bytes, a plane "
+            SDN_FAIL("%d x %d -> %d x %d does not fit the LDS plan: the output rows %d .. %d need %d source rows of %d bytes, a plane "
                       "holds %d", H, W, p.oh, p.ow, r0, r1 - 1, count, p.ow, rows_cap);
     }
     if (p.ytab < TRI_PLAN_INTS || p.xtab < TRI_PLAN_INTS || (long)p.ytab + p.oh > n || (long)p.xtab + p.ow > n)
-        PROP_FAIL("the zoom tables (%d, %d) lie outside the block of %ld ints", p.ytab, p.xtab, n);
+        SDN_FAIL("the zoom tables (%d, %d) lie outside the block of %ld ints", p.ytab, p.xtab, n);
     for (int y = 0; y < p.oh; y++)
-        if (T[p.ytab + y] < -1 || T[p.ytab + y] >= H) PROP_FAIL("zoom row %d reads row %d of %d", y, T[p.ytab + y], H);
+        if (T[p.ytab + y] < -1 || T[p.ytab + y] >= H) SDN_FAIL("zoom row %d reads row %d of %d", y, T[p.ytab + y], H);
     for (int x = 0; x < p.ow; x++)
-        if (T[p.xtab + x] < -1 || T[p.xtab + x] >= W) PROP_FAIL("zoom column %d reads column %d of %d", x, T[p.xtab + x], W);
-    if (p.mean < TRI_PLAN_INTS || (long)p.mean + TRI_MEAN_INTS > n) PROP_FAIL("the mean table at %d lies outside the block of %ld ints", p.mean, n);
+        if (T[p.xtab + x] < -1 || T[p.xtab + x] >= W) SDN_FAIL("zoom column %d reads column %d of %d", x, T[p.xtab + x], W);
+    if (p.mean < TRI_PLAN_INTS || (long)p.mean + TRI_MEAN_INTS > n) SDN_FAIL("the mean table at %d lies outside the block of %ld ints", p.mean, n);
     return 0;
 }
 
@@ -165,11 +165,11 @@ inline int tri_validate_image(const void* frames, int B, int H, int W, const int
 {
     TriLayout L;
     if (tri_layout(B, H, W, 0, &L, msg, cap)) return 1;
-    if (!frames || !plan || !image) PROP_FAIL("frames, plan or image is NULL");
-    if (!workspace) PROP_FAIL("workspace is NULL");
-    if (workspace_bytes < L.total) PROP_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
-    if (prop_misaligned(plan, 4) || prop_misaligned(image, 4)) PROP_FAIL("plan and image must be aligned to 4 bytes");
-    if (prop_misaligned(workspace, 16)) PROP_FAIL("workspace must be aligned to 16 bytes");
+    if (!frames || !plan || !image) SDN_FAIL("frames, plan or image is NULL");
+    if (!workspace) SDN_FAIL("workspace is NULL");
+    if (workspace_bytes < L.total) SDN_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
+    if (misaligned(plan, 4) || misaligned(image, 4)) SDN_FAIL("plan and image must be aligned to 4 bytes");
+    if (misaligned(workspace, 16)) SDN_FAIL("workspace must be aligned to 16 bytes");
     return tri_validate_plan(plan_host, n_plan, H, W, msg, cap);
 }
 
@@ -180,19 +180,19 @@ inline int tri_validate_item(const void* frame, const void* inst_map, const void
 {
     TriLayout L;
     if (tri_layout(1, H, W, G, &L, msg, cap)) return 1;
-    if (G < 1) PROP_FAIL("G %d; 1 to %d instances are supported", G, TRI_MAX_BOXES);
+    if (G < 1) SDN_FAIL("G %d; 1 to %d instances are supported", G, TRI_MAX_BOXES);
     if (use_mini && (mh < 1 || mw < 1 || mh > TRI_MAX_MINI || mw > TRI_MAX_MINI))
-        PROP_FAIL("mini-masks of %d x %d; each side 1 to %d is supported", mh, mw, TRI_MAX_MINI);
-    if (!frame || !inst_map || !ids || !plan || !image) PROP_FAIL("frame, inst_map, ids, plan or image is NULL");
-    if (!boxes_int || !boxes || !boxes_norm || !masks || !areas || !bad) PROP_FAIL("boxes_int, boxes, boxes_norm, masks, areas or bad is NULL");
-    if (!workspace) PROP_FAIL("workspace is NULL");
-    if (workspace_bytes < L.total) PROP_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
-    if (prop_misaligned(inst_map, 4) || prop_misaligned(ids, 4) || prop_misaligned(plan, 4) || prop_misaligned(image, 4))
-        PROP_FAIL("inst_map, ids, plan and image must be aligned to 4 bytes");
-    if (prop_misaligned(boxes_int, 4) || prop_misaligned(boxes, 4) || prop_misaligned(boxes_norm, 4) || prop_misaligned(masks, 4) ||
-        prop_misaligned(areas, 4) || prop_misaligned(bad, 4))
-        PROP_FAIL("boxes_int, boxes, boxes_norm, masks, areas and bad must be aligned to 4 bytes");
-    if (prop_misaligned(workspace, 16)) PROP_FAIL("workspace must be aligned to 16 bytes");
+        SDN_FAIL("mini-masks of %d x %d; each side 1 to %d is supported", mh, mw, TRI_MAX_MINI);
+    if (!frame || !inst_map || !ids || !plan || !image) SDN_FAIL("frame, inst_map, ids, plan or image is NULL");
+    if (!boxes_int || !boxes || !boxes_norm || !masks || !areas || !bad) SDN_FAIL("boxes_int, boxes, boxes_norm, masks, areas or bad is NULL");
+    if (!workspace) SDN_FAIL("workspace is NULL");
+    if (workspace_bytes < L.total) SDN_FAIL("workspace %zu < %zu bytes", workspace_bytes, L.total);
+    if (misaligned(inst_map, 4) || misaligned(ids, 4) || misaligned(plan, 4) || misaligned(image, 4))
+        SDN_FAIL("inst_map, ids, plan and image must be aligned to 4 bytes");
+    if (misaligned(boxes_int, 4) || misaligned(boxes, 4) || misaligned(boxes_norm, 4) || misaligned(masks, 4) ||
+        misaligned(areas, 4) || misaligned(bad, 4))
+        SDN_FAIL("boxes_int, boxes, boxes_norm, masks, areas and bad must be aligned to 4 bytes");
+    if (misaligned(workspace, 16)) SDN_FAIL("workspace must be aligned to 16 bytes");
     return tri_validate_plan(plan_host, n_plan, H, W, msg, cap);
 }
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import detection_layer_util as u
+import makefile_rules
 from maskrcnn import detection_layer as dl   # the feature itself: without it this module does not import
 from maskrcnn import detections as det
 
@@ -151,9 +152,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_pair_test_and_the_clamp():
     csrc = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
     mk = open(os.path.join(csrc, 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'detection_layer.hip' in exact
-    assert re.search(r'obj/detection_layer\.o: detection_layer\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('detection_layer.hip')
     assert '-ffp-contract=off' in re.search(r'^EXACT\s*:=\s*(.*)$', mk, flags=re.M).group(1) and '-fno-slp-vectorize' in mk
     text = open(os.path.join(csrc, 'detection_layer.hip')).read()
     for h in ('nms_mask.h', 'prop_device.h', 'detection_layer_check.h'):

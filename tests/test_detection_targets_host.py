@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import detection_targets_util as u
+import makefile_rules
 from maskrcnn import detection_targets as dt   # the feature itself: without it this module does not import
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -185,9 +186,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 def test_the_kernels_are_built_exactly_and_use_no_shortcut():
     csrc = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
     mk = open(os.path.join(csrc, 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'detection_targets.hip' in exact
-    assert re.search(r'obj/detection_targets\.o: detection_targets\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('detection_targets.hip')
     assert '-ffp-contract=off' in re.search(r'^EXACT\s*:=\s*(.*)$', mk, flags=re.M).group(1) and '-fno-slp-vectorize' in mk
     assert '-fhip-fp32-correctly-rounded-divide-sqrt' in mk
     text = open(os.path.join(csrc, 'detection_targets.hip')).read()
@@ -203,7 +202,7 @@ def test_the_kernels_are_built_exactly_and_use_no_shortcut():
         assert word not in text
     assert len(re.findall(r'hipLaunchKernelGGL\(', text)) == 2                     # two dependent launches
     hdr = open(os.path.join(csrc, 'detection_targets_check.h')).read()
-    body = hdr[hdr.index('PROP_HD int dt_negative_count'):]
+    body = hdr[hdr.index('SDN_HD int dt_negative_count'):]
     body = body[:body.index('}')]
     assert 'double' in body and 'float' not in body and re.search(r'r \* \(double\)P;\s*return \(int\)\(product - \(double\)P\);', body)
 

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import encode_input_util as u
+import makefile_rules
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 for _p in (os.path.join(ROOT, '3d-sdn_amd'), os.path.join(ROOT, '3d-sdn_amd', 'textural')):
@@ -137,9 +138,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 
 
 def test_the_kernels_are_built_without_fma_contraction():
-    mk = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'encode_input.hip' in exact and re.search(r'obj/encode_input\.o: encode_input\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('encode_input.hip')
 
 
 # ---- refusals ------------------------------------------------------------------------------------------------------------------------

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import makefile_rules
 import mrcnn_loss_util as u
 from maskrcnn import losses   # the feature itself: without it this module does not import
 
@@ -121,10 +122,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 
 
 def test_the_kernels_are_built_without_fma_contraction():
-    mk = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'mrcnn_loss.hip' in exact
-    assert re.search(r'obj/mrcnn_loss\.o: mrcnn_loss\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('mrcnn_loss.hip')
 
 
 def test_the_constants_are_mirrored_and_the_sizes_come_from_the_library():

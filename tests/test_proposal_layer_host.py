@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import makefile_rules
 import proposal_layer_util as u
 from maskrcnn import proposals   # the feature itself: without it this module does not import
 
@@ -134,10 +135,8 @@ def test_header_binding_and_library_hold_the_entry_points():
 
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_nms_pair_test():
     csrc = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
-    mk = open(os.path.join(csrc, 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'proposal_layer.hip' in exact and 'raster_boxes.hip' in exact
-    assert re.search(r'obj/proposal_layer\.o: proposal_layer\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('proposal_layer.hip')
+    makefile_rules.assert_built_exactly('raster_boxes.hip')
     shared = open(os.path.join(csrc, 'nms_mask.h')).read()
     assert len(re.findall(r'bool suppresses\(', shared)) == 1 and len(re.findall(r'void nms_mask_block\(', shared)) == 1
     for f in ('raster_boxes.hip', 'proposal_layer.hip'):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import makefile_rules
 import pyramid_roi_align_util as u
 from maskrcnn import pyramid   # the feature itself: without it this module does not import
 
@@ -120,10 +121,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_crops_sample():
     csrc = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
-    mk = open(os.path.join(csrc, 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'pyramid_roi_align.hip' in exact
-    assert re.search(r'obj/pyramid_roi_align\.o: pyramid_roi_align\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('pyramid_roi_align.hip')
     shared = open(os.path.join(csrc, 'crop_sample.h')).read()
     assert len(re.findall(r'float axis_in\(', shared)) == 1
     for f in ('raster_boxes.hip', 'pyramid_roi_align.hip'):

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import detection_layer_util as dlu
+import makefile_rules
 import predict_util as u
 import proposal_layer_util as plu
 from maskrcnn import predict as pr          # the feature itself: without it this module does not import
@@ -50,9 +51,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 
 
 def test_the_kernel_file_is_built_like_its_neighbours_and_uses_no_atomics():
-    mk = open(os.path.join(CSRC, 'Makefile')).read()
-    assert 'rpn_outputs.hip' in re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert re.search(r'obj/rpn_outputs\.o: rpn_outputs\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('rpn_outputs.hip')
     text = open(os.path.join(CSRC, 'rpn_outputs.hip')).read()
     assert '#include "rpn_outputs_check.h"' in text
     code = text.split('namespace sdn {')[1]
@@ -216,7 +215,9 @@ def test_the_headers_table_and_validators_walk_clean_under_asan_and_ubsan(tmp_pa
     src = os.path.join(ROOT, 'tools', 'rpn_outputs_check.cpp')
     text = open(src).read()
     assert re.findall(r'#include "([^"]+)"', text) == ['rpn_outputs_check.h'] and 'int main()' in text and 'hip' not in text.lower()
-    assert not re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'rpn_outputs_check.h')).read())     # the header stands alone
+    # the header stands alone: no other operation's header, only the macros every check header shares (plain C++ as well)
+    assert re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'rpn_outputs_check.h')).read()) == ['check_common.h']
+    assert not re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'check_common.h')).read())
     exe = str(tmp_path / 'rpn_outputs_check')
     # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
     static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']

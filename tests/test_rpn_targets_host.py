@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 import torch
 
+import makefile_rules
 import rpn_targets_util as u
 from maskrcnn import rpn_targets as rt   # the feature itself: without it this module does not import
 
@@ -194,9 +195,7 @@ def test_header_binding_and_library_hold_the_entry_points():
 def test_the_kernels_are_built_exactly_and_use_no_shortcut():
     csrc = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
     mk = open(os.path.join(csrc, 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'rpn_targets.hip' in exact
-    assert re.search(r'obj/rpn_targets\.o: rpn_targets\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('rpn_targets.hip')
     assert '-ffp-contract=off' in re.search(r'^EXACT\s*:=\s*(.*)$', mk, flags=re.M).group(1) and 'fast-math' not in mk
     text = open(os.path.join(csrc, 'rpn_targets.hip')).read()
     for h in ('rank_select.h', 'rpn_targets_check.h'):

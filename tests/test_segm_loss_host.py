@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 import torch
 
+import makefile_rules
 import segm_loss_util as u
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -74,10 +75,7 @@ def test_the_abi_revision_is_20_everywhere():
 
 
 def test_the_kernels_are_built_without_fma_contraction():
-    mk = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'segm_loss.hip' in exact
-    assert re.search(r'obj/segm_loss\.o: segm_loss\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('segm_loss.hip')
 
 
 def test_the_block_constant_is_mirrored():

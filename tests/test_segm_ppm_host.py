@@ -10,6 +10,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+import makefile_rules
 import segm_ppm_util as u
 
 
@@ -204,9 +205,7 @@ def test_the_kernels_are_built_without_fma_contraction():
     import os
     import re
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    mk = open(os.path.join(root, '3d-sdn_amd', 'csrc', 'Makefile')).read()
-    exact = re.search(r'^EXACT_SRC\s*:=\s*(.*)$', mk, flags=re.M).group(1).split()
-    assert 'segm_ppm.hip' in exact and re.search(r'obj/segm_ppm\.o: segm_ppm\.hip.*\n\t\$\(HIPCC\) \$\(COMMON\) \$\(EXACT\)', mk)
+    makefile_rules.assert_built_exactly('segm_ppm.hip')
 
 
 # ---- use_device_ppm on a CPU module ------------------------------------------------------------------------------------------------
