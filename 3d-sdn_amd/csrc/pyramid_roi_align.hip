@@ -18,6 +18,10 @@
 //               the direct fp32 atomic adds of k_crop_bwd and the reference's CUDA kernel: few samples fall on each of its pixels).
 //               Levels without a box stay all zero.  The order of the adds is not fixed, so the gradients are not bit-reproducible
 //               from run to run; with one add per box and pixel they stay within a few ulp of the exact sum.
+//   k_pra_box_records, k_pra_bwd_ordered   the second backward, sdn_pyramid_roi_align_bwd_ordered: a record per box (level, touched
+//               window), then a workgroup per (level, 8 x 8 tile, channel chunk) that gathers from the boxes whose window meets its
+//               tile, in ascending box index, into fp64 sums in registers, and stores every element once.  No float atomics, no
+//               zero fill: the same bits every run.  Described where the kernels stand.
 //
 // A non-finite level value (a box of area <= 0, NaN) gives level 2: pyramid_roi_align_check.h, pra_level_of.
 #include "crop_sample.h"
@@ -225,6 +229,159 @@ __global__ __launch_bounds__(PRA_THREADS) void k_pra_bwd(const PraParams P)
     }
 }
 
+// ---- the ordered backward: a gather per destination, no float atomics, no zero fill ---------------------------------------------------
+struct PraOrdParams {
+    const float* boxes;          // [R, 4]
+    const float* grads;          // [R, C, pool, pool]
+    int4* records;               // the workspace: two int4 per box -- (level index or -1, r0, r1, q0), (q1, 0, 0, 0)
+    float* gmap[PRA_LEVELS];
+    int H[PRA_LEVELS], W[PRA_LEVELS];
+    int start[PRA_LEVELS];       // first workgroup of level 3 - k: P5 comes first, its few tiles meet the most boxes each
+    int R, C, pool, chunks;
+    float image_area;
+};
+
+// A lane per box: the level and the window of the level's map that the box's samples can touch (pra_axis_range), for every workgroup of
+// k_pra_bwd_ordered to test against its tile.
+__global__ __launch_bounds__(PRA_THREADS) void k_pra_box_records(const PraOrdParams P)
+{
+    const int r = blockIdx.x * PRA_THREADS + threadIdx.x;
+    if (r >= P.R) return;
+    const float* box = P.boxes + 4 * (size_t)r;
+    const float y1 = box[0], x1 = box[1], y2 = box[2], x2 = box[3];
+    int l = pra_level_of(pra_level_value(y1, x1, y2, x2, P.image_area)) - 2;
+    const int H = l == 0 ? P.H[0] : l == 1 ? P.H[1] : l == 2 ? P.H[2] : P.H[3];
+    const int W = l == 0 ? P.W[0] : l == 1 ? P.W[1] : l == 2 ? P.W[2] : P.W[3];
+    int r0 = 0, r1 = 0, q0 = 0, q1 = 0;
+    if (!pra_axis_range(y1, y2, H, P.pool, &r0, &r1) || !pra_axis_range(x1, x2, W, P.pool, &q0, &q1)) l = -1;   // no sample inside
+    P.records[2 * (size_t)r] = make_int4(l, r0, r1, q0);
+    P.records[2 * (size_t)r + 1] = make_int4(q1, 0, 0, 0);
+}
+
+// A workgroup owns one level, one tile of PRA_TILE x PRA_TILE pixels and one chunk of PRA_CHANNELS channels, and stores every element
+// of that block exactly once.  A lane owns one pixel (the wave's 64 lanes are the tile) and the channels c0 + wave + 4 i, i < 16, with
+// an fp64 sum each in registers.  The boxes are taken in ascending index: 256 records at a time, ballot-compacted in index order into
+// an LDS list of those of this level whose window meets the tile.  Of PRA_ORD_BATCH listed boxes at a time the per-axis tables stand
+// in the LDS -- per sample index the low and high pixel index (-1: outside) and the lerp weight, the arithmetic of pra_prepare; the
+// weights are separable, so pool entries per axis replace the pool x pool table.  axis_in is monotonic in the sample index, so the
+// samples that touch a lane's row (column) are a contiguous range: the lane finds its two ranges in the tables and runs over their
+// product only, first to last, adding the terms of crop_and_resize.c:241-247 in the C code's order.  The order of all additions is
+// thus (box, sy, sx, tap): a function of the arguments alone.
+__global__ __launch_bounds__(PRA_THREADS) void k_pra_bwd_ordered(const PraOrdParams P)
+{
+    constexpr int WAVES = PRA_THREADS / 64, PER_LANE = PRA_CHANNELS / WAVES;
+    static_assert(PRA_TILE * PRA_TILE == 64 && PER_LANE == 16, "a wave is a tile; 16 sums per lane");
+    __shared__ int list[PRA_THREADS];
+    __shared__ int wave_count[WAVES];
+    __shared__ int tab_lo[PRA_ORD_BATCH][2][PRA_MAX_POOL], tab_hi[PRA_ORD_BATCH][2][PRA_MAX_POOL];
+    __shared__ float tab_lerp[PRA_ORD_BATCH][2][PRA_MAX_POOL];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int k = (b >= P.start[1]) + (b >= P.start[2]) + (b >= P.start[3]);   // the same in every lane
+    const int l = PRA_LEVELS - 1 - k;
+    const int idx = b - (k == 0 ? P.start[0] : k == 1 ? P.start[1] : k == 2 ? P.start[2] : P.start[3]);
+    const int H = l == 0 ? P.H[0] : l == 1 ? P.H[1] : l == 2 ? P.H[2] : P.H[3];
+    const int W = l == 0 ? P.W[0] : l == 1 ? P.W[1] : l == 2 ? P.W[2] : P.W[3];
+    float* gmap = l == 0 ? P.gmap[0] : l == 1 ? P.gmap[1] : l == 2 ? P.gmap[2] : P.gmap[3];
+    const int tiles_x = pra_tiles(W), tiles = tiles_x * pra_tiles(H);
+    const int chunk = idx / tiles, tile = idx - chunk * tiles;
+    const int ty0 = tile / tiles_x * PRA_TILE, tx0 = (tile - tile / tiles_x * tiles_x) * PRA_TILE;
+    const int row = ty0 + lane / PRA_TILE, col = tx0 + lane % PRA_TILE;   // a pixel beyond the map's edge matches no sample
+    const int c0 = chunk * PRA_CHANNELS, nc = min(PRA_CHANNELS, P.C - c0);
+    const int mine = (nc - wave + WAVES - 1) / WAVES;   // channels c0 + wave + 4 i below c0 + nc; 0 for a wave past a short chunk
+    const int pool = P.pool, pp = pool * pool;
+    double acc[PER_LANE];
+#pragma unroll
+    for (int i = 0; i < PER_LANE; i++) acc[i] = 0.0;
+
+    for (int base = 0; base < P.R; base += PRA_THREADS) {
+        const int r = base + tid;
+        bool hit = false;
+        if (r < P.R) {
+            const int4 a = P.records[2 * (size_t)r], q = P.records[2 * (size_t)r + 1];
+            hit = a.x == l && a.y <= ty0 + PRA_TILE - 1 && a.z >= ty0 && a.w <= tx0 + PRA_TILE - 1 && q.x >= tx0;
+        }
+        const unsigned long long votes = __ballot(hit);
+        if (lane == 0) wave_count[wave] = __popcll(votes);
+        __syncthreads();
+        int before = 0, n = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; w++) {
+            before += w < wave ? wave_count[w] : 0;
+            n += wave_count[w];
+        }
+        if (hit) list[before + __popcll(votes & ((1ull << lane) - 1ull))] = r;   // ascending box index
+        __syncthreads();
+        for (int b0 = 0; b0 < n; b0 += PRA_ORD_BATCH) {
+            const int nb = min(PRA_ORD_BATCH, n - b0);
+            for (int e = tid; e < nb * 2 * PRA_MAX_POOL; e += PRA_THREADS) {
+                const int j = e / (2 * PRA_MAX_POOL), axis = e / PRA_MAX_POOL % 2, s = e % PRA_MAX_POOL;
+                if (s >= pool) continue;
+                const float* box = P.boxes + 4 * (size_t)list[b0 + j];
+                const int extent = axis ? W : H;
+                const float in = axis_in(box[axis], box[axis + 2], extent, pool, s);
+                int lo = -1, hi = -1;
+                float lerp = 0.0f;
+                if (axis_inside(in, extent)) {   // 0 <= in <= extent - 1
+                    lo = (int)floorf(in);
+                    hi = (int)ceilf(in);
+                    lerp = in - (float)lo;
+                }
+                tab_lo[j][axis][s] = lo;
+                tab_hi[j][axis][s] = hi;
+                tab_lerp[j][axis][s] = lerp;
+            }
+            __syncthreads();
+            for (int j = 0; j < nb; j++) {
+                int sy0 = pool, sy1 = -1, sx0 = pool, sx1 = -1;
+                for (int s = 0; s < pool; s++) {
+                    if (tab_lo[j][0][s] == row || tab_hi[j][0][s] == row) {
+                        sy0 = min(sy0, s);
+                        sy1 = s;
+                    }
+                    if (tab_lo[j][1][s] == col || tab_hi[j][1][s] == col) {
+                        sx0 = min(sx0, s);
+                        sx1 = s;
+                    }
+                }
+                if (sy1 < 0 || sx1 < 0 || mine == 0) continue;
+                const float* g_box = P.grads + ((size_t)list[b0 + j] * P.C + c0 + wave) * pp;
+                for (int sy = sy0; sy <= sy1; sy++) {
+                    const bool on_top = tab_lo[j][0][sy] == row, on_bottom = tab_hi[j][0][sy] == row;
+                    if (!on_top && !on_bottom) continue;
+                    const float y_lerp = tab_lerp[j][0][sy];
+                    for (int sx = sx0; sx <= sx1; sx++) {
+                        const bool on_left = tab_lo[j][1][sx] == col, on_right = tab_hi[j][1][sx] == col;
+                        if (!on_left && !on_right) continue;
+                        const float x_lerp = tab_lerp[j][1][sx];
+                        const float* g_in = g_box + sy * pool + sx;
+#pragma unroll
+                        for (int i = 0; i < PER_LANE; i++) {
+                            if (i >= mine) continue;
+                            const float g = g_in[(size_t)i * WAVES * pp];
+                            const float dtop = (1.0f - y_lerp) * g, dbottom = y_lerp * g;   // crop_and_resize.c:241-247
+                            // a sample on a pixel row or column has low == high: both of its terms land here and both are added
+                            if (on_top && on_left) acc[i] += (double)((1.0f - x_lerp) * dtop);
+                            if (on_top && on_right) acc[i] += (double)(x_lerp * dtop);
+                            if (on_bottom && on_left) acc[i] += (double)((1.0f - x_lerp) * dbottom);
+                            if (on_bottom && on_right) acc[i] += (double)(x_lerp * dbottom);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (row < H && col < W) {
+        float* out = gmap + (size_t)(c0 + wave) * H * W + (size_t)row * W + col;
+#pragma unroll
+        for (int i = 0; i < PER_LANE; i++)
+            if (i < mine) out[(size_t)i * WAVES * H * W] = (float)acc[i];
+    }
+    // the level's first workgroup also writes the floats that pad its range to 16 bytes
+    const size_t used = (size_t)P.C * H * W;
+    if (idx == 0 && tid < (int)((PRA_ALIGN_FLOATS - used % PRA_ALIGN_FLOATS) % PRA_ALIGN_FLOATS)) gmap[used + tid] = 0.0f;
+}
+
 static PraParams pra_params(const float* boxes, const int* H, const int* W, int C, int pool, float image_area)
 {
     PraParams P = {};
@@ -287,4 +444,46 @@ SDN_API int sdn_pyramid_roi_align_bwd(const float* grads, const float* boxes, in
     P.grads = grads;
     hipLaunchKernelGGL(k_pra_bwd, dim3((unsigned)R * (unsigned)P.chunks), dim3(PRA_THREADS), pra_table_bytes(pool), st, P);
     return check_launch("k_pra_bwd");
+}
+
+SDN_API int sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(int R, size_t* bytes)
+{
+    char why[256];
+    if (pra_ordered_workspace_bytes(R, bytes, why, sizeof(why))) return fail(SDN_EINVAL, "sdn_pyramid_roi_align_bwd_ordered_workspace_bytes: %s", why);
+    return SDN_OK;
+}
+
+SDN_API int sdn_pyramid_roi_align_bwd_ordered(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
+                                              float image_area, float* grad_maps, void* workspace, size_t workspace_bytes, sdnStream stream)
+{
+    char why[256];
+    if (pra_validate_bwd_ordered(grads, boxes, H, W, R, C, pool, image_area, grad_maps, workspace, workspace_bytes, why, sizeof(why)))
+        return fail(SDN_EINVAL, "sdn_pyramid_roi_align_bwd_ordered: %s", why);
+    size_t offsets[PRA_LEVELS], total = 0;
+    if (pra_grad_layout(C, H, W, offsets, &total, why, sizeof(why))) return fail(SDN_EINVAL, "sdn_pyramid_roi_align_bwd_ordered: %s", why);
+    hipStream_t st = (hipStream_t)stream;
+    PraOrdParams P = {};
+    P.boxes = boxes;
+    P.grads = grads;
+    P.records = static_cast<int4*>(workspace);
+    P.R = R;
+    P.C = C;
+    P.pool = pool;
+    P.chunks = pra_chunks(C);
+    P.image_area = image_area;
+    int blocks = 0;
+    for (int k = 0; k < PRA_LEVELS; k++) {   // P5 first
+        const int l = PRA_LEVELS - 1 - k;
+        P.H[l] = H[l];
+        P.W[l] = W[l];
+        P.gmap[l] = grad_maps + offsets[l];
+        P.start[k] = blocks;
+        blocks += pra_tiles(H[l]) * pra_tiles(W[l]) * P.chunks;   // the sum is below 2^31: pra_validate_bwd_ordered
+    }
+    if (R > 0) {
+        hipLaunchKernelGGL(k_pra_box_records, dim3((unsigned)((R + PRA_THREADS - 1) / PRA_THREADS)), dim3(PRA_THREADS), 0, st, P);
+        if (int rc = check_launch("k_pra_box_records")) return rc;
+    }
+    hipLaunchKernelGGL(k_pra_bwd_ordered, dim3((unsigned)blocks), dim3(PRA_THREADS), 0, st, P);
+    return check_launch("k_pra_bwd_ordered");
 }

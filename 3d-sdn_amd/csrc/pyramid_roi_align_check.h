@@ -20,7 +20,13 @@ constexpr int PRA_MAX_POOL = 32;      // the sample table of pool x pool entries
 constexpr int PRA_SAMPLE_BYTES = 28;  // four tap offsets (int), two lerp weights (float), an inside flag (int)
 constexpr int PRA_ALIGN_FLOATS = 4;   // every level's gradient range starts on 16 bytes: the zero fill stores 16 bytes at a time
 
+// the ordered backward (k_pra_box_records, k_pra_bwd_ordered): a workgroup owns (level, tile of PRA_TILE x PRA_TILE pixels, channel chunk)
+constexpr int PRA_TILE = 8;           // 64 pixels, one per lane of a wave; the four waves share the chunk's channels: 16 fp64 sums per lane
+constexpr int PRA_RECORD_BYTES = 32;  // workspace per box: level (or -1: no sample inside), window r0, r1, q0, q1, three unused ints
+constexpr int PRA_ORD_BATCH = 8;      // boxes whose per-axis tables stand in the LDS at once
+
 SDN_HD int pra_chunks(int C) { return (C + PRA_CHANNELS - 1) / PRA_CHANNELS; }
+SDN_HD int pra_tiles(int extent) { return (extent - 1) / PRA_TILE + 1; }   // extent >= 1; no overflow at INT_MAX
 SDN_HD size_t pra_table_bytes(int pool) { return (size_t)pool * (size_t)pool * PRA_SAMPLE_BYTES; }
 
 // model.py:456-457 on the value of :455: round half to even (torch.round, rintf in the default rounding mode), then clamp to [2, 5].
@@ -105,6 +111,41 @@ inline int pra_validate_bwd(const void* grads, const void* boxes, const int* H, 
     if (R == 0) return 0;
     if (!grads || !boxes) SDN_FAIL("grads or boxes is NULL with R > 0");
     if (misaligned(grads, 4) || misaligned(boxes, 4)) SDN_FAIL("grads and boxes must be aligned to 4 bytes");
+    return 0;
+}
+
+// ---- the ordered backward -----------------------------------------------------------------------------------------------------------
+// bytes of the workspace of sdn_pyramid_roi_align_bwd_ordered: one record per box
+inline int pra_ordered_workspace_bytes(int R, size_t* bytes, char* msg, size_t cap)
+{
+    if (R < 0) SDN_FAIL("bad sizes: R %d", R);
+    if (!bytes) SDN_FAIL("bytes is NULL");
+    *bytes = (size_t)R * PRA_RECORD_BYTES;
+    return 0;
+}
+
+// workgroups of k_pra_bwd_ordered: every tile of every level, once per channel chunk.  Valid sizes only (pra_validate_maps): a level has
+// at most 2^31 / 8 tiles (H * W < 2^31), so four levels times the chunks fit a long long with room to spare.
+inline long long pra_ordered_blocks(int C, const int* H, const int* W)
+{
+    long long tiles = 0;
+    for (int l = 0; l < PRA_LEVELS; l++) tiles += (long long)pra_tiles(H[l]) * pra_tiles(W[l]);
+    return tiles * pra_chunks(C);
+}
+
+inline int pra_validate_bwd_ordered(const void* grads, const void* boxes, const int* H, const int* W, int R, int C, int pool, float image_area,
+                                    const void* grad_maps, const void* workspace, size_t workspace_bytes, char* msg, size_t cap)
+{
+    if (pra_validate_bwd(grads, boxes, H, W, R, C, pool, image_area, grad_maps, msg, cap)) return 1;
+    // sizes that passed above give at most 2^30 (four levels of 1 x (2^31 - 1)); the test stands so that another PRA_TILE or
+    // PRA_CHANNELS cannot overflow the grid unnoticed
+    const long long blocks = pra_ordered_blocks(C, H, W);
+    if (blocks > INT_MAX) SDN_FAIL("%lld tiles of %d x %d pixels times channel chunks must stay below 2^31 workgroups", blocks, PRA_TILE, PRA_TILE);
+    if (R == 0) return 0;   // no record is written or read
+    if (!workspace) SDN_FAIL("workspace is NULL with R > 0");
+    if (misaligned(workspace, 16)) SDN_FAIL("workspace must be aligned to 16 bytes");
+    const size_t need = (size_t)R * PRA_RECORD_BYTES;
+    if (workspace_bytes < need) SDN_FAIL("workspace of %zu bytes; %zu are needed for %d boxes", workspace_bytes, need, R);
     return 0;
 }
 

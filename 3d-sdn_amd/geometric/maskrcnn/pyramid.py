@@ -8,8 +8,11 @@ The reference walks the four levels on the host: per level an ix.any() and a tor
 index gather, one crop, and at the end two cats, a sort and a gather that copies the whole result once more.  Here a box's level is
 computed where the box is sampled and row r of the result is box r: one launch forward, a zero fill and one scatter launch backward,
 nothing crosses to the host.  The kernels are csrc/pyramid_roi_align.hip behind sdn_hip.ops.pyramid_roi_align; CPU tensors raise
-NotImplementedError and there is no torch form.  The values are those of the reference's crop_and_resize.c bit for bit; the map
-gradients are sums of fp32 atomic adds (as in the reference's CUDA kernel) and so not bit-reproducible from run to run.
+NotImplementedError and there is no torch form.  The values are those of the reference's crop_and_resize.c bit for bit; by default
+the map gradients are sums of fp32 atomic adds (as in the reference's CUDA kernel) and so not bit-reproducible from run to run.
+Under torch.use_deterministic_algorithms(True) or SDN_DETERMINISTIC=1 the backward is a record launch and one gather launch
+instead (sdn_pyramid_roi_align_bwd_ordered): every gradient element is a fixed-order sum stored once, the same bits every run;
+sdn_hip.ops.pyramid_backward_path() tells which of the two a backward would take.
 """
 import torch
 

@@ -134,6 +134,8 @@ def _declare(L):
     sig['sdn_pyramid_roi_align_grad_floats'] = [_ci, _ip, _ip, ctypes.POINTER(_sz), ctypes.POINTER(_sz)]
     sig['sdn_pyramid_roi_align_fwd'] = [_vp, _ci, ctypes.POINTER(_vp), _ip, _ip, _ci, _ci, _cf, _cf, _vp, _vp, _vp]
     sig['sdn_pyramid_roi_align_bwd'] = [_vp, _vp, _ci, _ip, _ip, _ci, _ci, _cf, _vp, _vp]
+    sig['sdn_pyramid_roi_align_bwd_ordered_workspace_bytes'] = [_ci, ctypes.POINTER(_sz)]
+    sig['sdn_pyramid_roi_align_bwd_ordered'] = [_vp, _vp, _ci, _ip, _ip, _ci, _ci, _cf, _vp, _vp, _sz, _vp]
     sig['sdn_proposal_layer_workspace_bytes'] = [_ci, _ci, _ci, ctypes.POINTER(_sz)]
     sig['sdn_proposal_layer'] = [_vp, _vp, _vp, _ci, ctypes.POINTER(_cf), _ci, _ci, _ci, _ci, _cf, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]
     sig['sdn_detection_layer_workspace_bytes'] = [_ci, _ci, _ci, ctypes.POINTER(_sz)]
@@ -187,7 +189,7 @@ def _declare(L):
         try:
             fn = getattr(L, name)
         except AttributeError:
-            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*, sdn_pyramid_roi_align_*, sdn_proposal_layer*, sdn_detection_layer*, sdn_detection_targets*, sdn_rpn_targets*, sdn_training_item*, sdn_rpn_outputs_*): a library built before them is stale
+            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*, sdn_pyramid_roi_align_*, sdn_proposal_layer*, sdn_detection_layer*, sdn_detection_targets*, sdn_rpn_targets*, sdn_training_item*, sdn_rpn_outputs_*, sdn_pyramid_roi_align_bwd_ordered*): a library built before them is stale
             raise SdnHipError('%s does not export %s -- rebuild it (`python __graft_entry__.py build`)' % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = _ci
@@ -235,6 +237,7 @@ def exported_symbols():
             'sdn_encode_maps', 'sdn_inst_index_workspace_bytes', 'sdn_inst_index_build', 'sdn_inst_index_rank',
             'sdn_mrcnn_loss_workspace_bytes', 'sdn_mrcnn_loss_fwd', 'sdn_mrcnn_loss_bwd',
             'sdn_pyramid_roi_align_grad_floats', 'sdn_pyramid_roi_align_fwd', 'sdn_pyramid_roi_align_bwd',
+            'sdn_pyramid_roi_align_bwd_ordered_workspace_bytes', 'sdn_pyramid_roi_align_bwd_ordered',
             'sdn_proposal_layer_workspace_bytes', 'sdn_proposal_layer',
             'sdn_detection_layer_workspace_bytes', 'sdn_detection_layer',
             'sdn_detection_targets_workspace_bytes', 'sdn_detection_targets',
@@ -246,6 +249,13 @@ def exported_symbols():
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',
             'sdn_render_maps_bwd', 'sdn_program_create', 'sdn_program_run',
             'sdn_program_destroy']
+
+
+def deterministic():
+    """The one rule for "deterministic": torch's own switch -- torch.use_deterministic_algorithms(True) -- or SDN_DETERMINISTIC=1.
+    With it on, every path that would combine sums with float atomics takes its fixed-order form: the conv stack's split-K sums
+    (sdn_hip.conv) and the pyramid RoIAlign's backward (sdn_hip.ops.pyramid_backward_path).  Read when a call runs, not at import."""
+    return torch.are_deterministic_algorithms_enabled() or os.environ.get('SDN_DETERMINISTIC') == '1'
 
 
 def check(rc):

@@ -27,6 +27,7 @@ import weakref
 import torch
 
 from . import check, lib, stream
+from . import deterministic as _deterministic
 from . import convplan as cp
 from . import program as pg
 
@@ -73,8 +74,9 @@ def _tag(t):
 
 def deterministic():
     """True: split-K partial sums are combined in a fixed order (bit-reproducible gradients) instead of with float
-    atomics.  Follows torch's own switch -- torch.use_deterministic_algorithms(True) -- or SDN_DETERMINISTIC=1."""
-    return torch.are_deterministic_algorithms_enabled() or os.environ.get('SDN_DETERMINISTIC') == '1'
+    atomics.  Follows torch's own switch -- torch.use_deterministic_algorithms(True) -- or SDN_DETERMINISTIC=1: the package's
+    one rule, sdn_hip.deterministic."""
+    return _deterministic()
 
 
 _side_streams = {}

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, lib, ptr, raster_bwd_workspace,
+from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, deterministic, lib, ptr, raster_bwd_workspace,
                raster_workspace, scene_id_workspace, stream, train_id_workspace, want)
 
 CAMERA_NONE, CAMERA_LOOK, CAMERA_LOOK_AT = 0, 1, 2
@@ -1741,10 +1741,25 @@ def pyramid_grad_floats(C, H, W):
     return list(offsets), total.value
 
 
+def pyramid_backward_path():
+    """'ordered' or 'atomic': the backward a pyramid_roi_align gradient takes if it runs now.  'ordered' under
+    torch.use_deterministic_algorithms(True) or SDN_DETERMINISTIC=1 (sdn_hip.deterministic): sdn_pyramid_roi_align_bwd_ordered, a
+    gather per destination in a fixed order, the same bits every run.  'atomic' otherwise: sdn_pyramid_roi_align_bwd."""
+    return 'ordered' if deterministic() else 'atomic'
+
+
+def pyramid_ordered_workspace_bytes(R):
+    """bytes of the workspace of sdn_pyramid_roi_align_bwd_ordered for R boxes, asked of the library"""
+    n = ctypes.c_size_t(0)
+    check(lib().sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(int(R), ctypes.byref(n)))
+    return n.value
+
+
 class PyramidRoiAlignFn(torch.autograd.Function):
-    """pyramid_roi_align of the reference's Mask R-CNN (geometric/maskrcnn/model.py:414-502) -- sdn_pyramid_roi_align_fwd / _bwd
-    (include/sdn_hip.h), forward in one launch, backward in a zero fill and one scatter launch.  Returns (pooled fp32 [R, C, pool,
-    pool] in box order, levels int32 [R]).  `pyramid_roi_align` below checks types and shapes."""
+    """pyramid_roi_align of the reference's Mask R-CNN (geometric/maskrcnn/model.py:414-502) -- sdn_pyramid_roi_align_fwd / _bwd /
+    _bwd_ordered (include/sdn_hip.h), forward in one launch, backward in a zero fill and one scatter launch, or, where
+    pyramid_backward_path() says 'ordered' when the backward runs, in a record launch and one gather launch.  Returns (pooled fp32
+    [R, C, pool, pool] in box order, levels int32 [R]).  `pyramid_roi_align` below checks types and shapes."""
 
     @staticmethod
     def forward(ctx, boxes, p2, p3, p4, p5, pool, image_area):
@@ -1774,7 +1789,13 @@ class PyramidRoiAlignFn(torch.autograd.Function):
             g = g_pooled.to(torch.float32).contiguous()
             offsets, total = pyramid_grad_floats(C, H, W)
             buf = torch.empty(total, dtype=torch.float32, device=boxes.device)
-            check(lib().sdn_pyramid_roi_align_bwd(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf), stream()))
+            if pyramid_backward_path() == 'ordered':
+                nbytes = pyramid_ordered_workspace_bytes(R)
+                ws = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device) if nbytes else None   # the caching allocator aligns to 512
+                check(lib().sdn_pyramid_roi_align_bwd_ordered(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf),
+                                                              ptr(ws), nbytes, stream()))
+            else:
+                check(lib().sdn_pyramid_roi_align_bwd(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf), stream()))
         views = [buf[o:o + C * h * w].view(C, h, w) if need else None for o, h, w, need in zip(offsets, H, W, ctx.needs_input_grad[1:5])]
         return (None,) + tuple(views) + (None, None)
 
@@ -1784,8 +1805,10 @@ def pyramid_roi_align(boxes, maps, pool, image_area):
     (y1, x1, y2, x2) normalised, maps = (P2, P3, P4, P5), each fp32 [C, H_l, W_l], image_area = float(image_shape[0] * image_shape[1]).
     Row r of pooled is box r, sampled with crop_and_resize's arithmetic from level levels[r] (2 .. 5; a box of area <= 0 or with a NaN
     goes to level 2).  Differentiable in the four maps only: the boxes get None (the reference detaches them, :473), levels is not
-    differentiable.  The four gradients are views of one buffer; they are sums of fp32 atomic adds and so not bit-reproducible from
-    run to run.  Nothing is copied to the host in either direction.  A wrong type or dtype raises TypeError, a wrong shape or a
+    differentiable.  The four gradients are views of one buffer; by default they are sums of fp32 atomic adds and so not bit-reproducible from
+    run to run.  Under torch.use_deterministic_algorithms(True) or SDN_DETERMINISTIC=1, read when the backward runs
+    (pyramid_backward_path()), they are fixed-order fp64 sums of the reference's fp32 terms rounded once: the same bits every run.
+    Nothing is copied to the host in either direction.  A wrong type or dtype raises TypeError, a wrong shape or a
     non-contiguous tensor ValueError, a CPU tensor NotImplementedError."""
     maps = tuple(maps)
     if len(maps) != PYRAMID_LEVELS:

@@ -80,7 +80,8 @@ const char* sdn_last_error(void);
  * sdn_pyramid_roi_align_bwd added; still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added; still 20:
  * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
  * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added; still 20: sdn_training_item_workspace_bytes,
- * sdn_training_item_image, sdn_training_item added; still 20: sdn_rpn_outputs_fwd, sdn_rpn_outputs_bwd added -- new entry
+ * sdn_training_item_image, sdn_training_item added; still 20: sdn_rpn_outputs_fwd, sdn_rpn_outputs_bwd added; still 20:
+ * sdn_pyramid_roi_align_bwd_ordered_workspace_bytes, sdn_pyramid_roi_align_bwd_ordered added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1066,6 +1067,20 @@ int sdn_pyramid_roi_align_fwd(const float* boxes, int R, const float* const* map
                               float image_area, float extrapolation, float* pooled, int32_t* levels, sdnStream stream);
 int sdn_pyramid_roi_align_bwd(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
                               float image_area, float* grad_maps, sdnStream stream);
+/* The ORDERED backward of the pyramid RoIAlign: the same arguments, the same grad_maps layout, level rule and sample arithmetic as
+ * sdn_pyramid_roi_align_bwd, but bit-reproducible: no float atomics and no zero fill.  Every element of grad_maps -- the padding
+ * between the levels and whole levels without a box included -- is stored exactly once by a plain store.  Its value: the four fp32
+ * terms of every inside sample that lands on it, formed operation for operation as crop_and_resize.c:241-247 (a sample on a pixel
+ * row or column sends two terms to one pixel, both are added, so 0 * inf gives NaN as there), widened to fp64, added to +0.0 in an
+ * order that depends on the arguments' values only (ascending box, then sample row, sample column, tap), rounded to fp32 once.
+ * TWO launches: a record per box (level, touched window) into `workspace`, then one workgroup per (level, tile of 8 x 8 pixels, chunk
+ * of 64 channels) that gathers from the boxes whose window meets its tile.  workspace: caller-owned, 16-byte aligned, at least
+ * sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(R) bytes (32 per box; R = 0 needs none and may pass NULL; the whole buffer is
+ * then +0.0).  Nothing crosses to the host; the call can be captured in a graph.  SDN_EINVAL as _bwd, and for: workspace NULL,
+ * misaligned or too small with R > 0; the query refuses R < 0 and a NULL `bytes`. */
+int sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(int R, size_t* bytes);
+int sdn_pyramid_roi_align_bwd_ordered(const float* grads, const float* boxes, int R, const int* H, const int* W, int C, int pool,
+                                      float image_area, float* grad_maps, void* workspace, size_t workspace_bytes, sdnStream stream);
 /* Proposal layer: proposal_layer of geometric/maskrcnn/model.py:344-407 with apply_box_deltas (:307-328) and clip_boxes (:331-341)
  * (csrc/proposal_layer.hip).  rpn_probs fp32 [A, 2] = (bg, fg); rpn_bbox fp32 [A, 4]; anchors fp32 [A, 4] = (y1, x1, y2, x2) in pixels;
  * std_dev: four floats in HOST memory, read during the call; 1 <= K <= min(A, 8192) anchors enter the NMS (the caller passes

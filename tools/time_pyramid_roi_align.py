@@ -4,12 +4,17 @@ maskrcnn/vkitti.py:30-41 change the class count only): a 1024 x 1024 image, P2 .
 pixels square), 256 channels; the classifier's call with POOL_SIZE 7 on POST_NMS_ROIS_INFERENCE = 1000 proposals and the mask
 head's with MASK_POOL_SIZE 14 on DETECTION_MAX_INSTANCES = 100 detections.  Prints one JSON line; per call shape
   device_fwd_ms, device_fwdbwd_ms   maskrcnn.pyramid.pyramid_roi_align (one launch), and with backward (a zero fill and one launch)
+  ordered_fwdbwd_ms                 the same forward with the ORDERED backward (SDN_DETERMINISTIC=1 while it runs: a record launch and
+                                    one gather launch, no zero fill, no atomics); checked first to give the same bytes twice
   loop_fwd_ms, loop_fwdbwd_ms       the reference's loop (model.py:445-500) written with this library's CropAndResizeFunction and
                                     torch, in the same process: the level formula, per level any / nonzero / gather / crop, the
                                     cats, the sort and the final gather; and with backward
   *_launches                        kernels per call as torch.profiler counts them (null where the profiler is unavailable)
   bytes                             what the call must move, from the shapes: forward the boxes, the pooled output and one read of
-                                    every tap; backward the incoming gradient, the zero fill and four atomic adds per sample
+                                    every tap; backward the incoming gradient, the zero fill and four atomic adds per sample;
+                                    bwd_ordered: the boxes, a 32-byte record per box, the incoming gradient once and ONE store of
+                                    the maps' gradients; tile_meetings counts the (box, 8 x 8 tile) pairs whose window and tile
+                                    meet -- each re-reads its part of the box's gradient, per 64-channel chunk, through the caches
 Each figure: --inner calls inside one synchronised region of the host clock, divided by --inner; the median of --reps such
 regions, the forms alternating inside every repetition, after --warmup calls of each; *_spread is (min, max) over the repetitions.
 The loop waits for the device eight times per call; the device form never does.  Checks first that both forms give the same bits
@@ -31,7 +36,8 @@ for p in (ROOT, os.path.join(ROOT, '3d-sdn_amd'), os.path.join(ROOT, '3d-sdn_amd
 IMAGE_SHAPE = (1024, 1024, 3)
 C = 256
 SIDES = (256, 128, 64, 32)
-CALLS = {'classifier_pool7_R1000': (7, 1000), 'mask_pool14_R100': (14, 100)}
+CALLS = {'classifier_pool7_R1000': (7, 1000), 'mask_pool14_R100': (14, 100),
+         'classifier_pool7_R200': (7, 200), 'mask_pool14_R200': (14, 200)}   # TRAIN_ROIS_PER_IMAGE = 200: the training chain's calls
 
 
 def loop_form(inputs, pool_size, image_shape, crop):
@@ -91,7 +97,23 @@ def count_launches(fn):
 def counted_bytes(R, pool):
     out = R * C * pool * pool * 4
     maps = sum(C * s * s * 4 for s in SIDES)
-    return {'fwd': R * 16 + out + 4 * out + R * 4, 'bwd': R * 16 + out + maps + 4 * out, 'pooled': out, 'maps': maps}
+    return {'fwd': R * 16 + out + 4 * out + R * 4, 'bwd': R * 16 + out + maps + 4 * out, 'bwd_ordered': R * 16 + 2 * R * 32 + out + maps,
+            'pooled': out, 'maps': maps}
+
+
+def tile_meetings(boxes, pool, tile=8):
+    """(box, tile) pairs of the ordered backward: tiles of the box's level that the window of its inside samples meets"""
+    sys.path.insert(0, os.path.join(ROOT, 'tests'))
+    import pyramid_roi_align_util as u
+    levels = u.levels_of(u.level_values(boxes))
+    n = 0
+    for box, lv in zip(boxes, levels):
+        side = SIDES[lv - 2]
+        inside, (tl, _tr, _bl, br), _xl, _yl = u.sample_table(box, side, side, pool)
+        if inside.any():
+            r0, r1, q0, q1 = tl[inside].min() // side, br[inside].max() // side, (tl[inside] % side).min(), (br[inside] % side).max()
+            n += int((r1 // tile - r0 // tile + 1) * (q1 // tile - q0 // tile + 1))
+    return n
 
 
 def draw_boxes(rs, R):
@@ -113,6 +135,7 @@ def main():
     ap.add_argument('--inner', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=10)
     a = ap.parse_args()
+    assert 'SDN_DETERMINISTIC' not in os.environ, 'unset SDN_DETERMINISTIC: the tool times both backward paths and sets it itself'
     from maskrcnn import pyramid
     from maskrcnn.roialign.roi_align.crop_and_resize import CropAndResizeFunction
     assert torch.cuda.is_available(), 'this tool measures on the GPU; there is no CPU form of it'
@@ -142,7 +165,16 @@ def main():
             clear()
             loop_fwd().backward(g)
 
-        forms = {'device_fwd': device_fwd, 'loop_fwd': loop_fwd, 'device_fwdbwd': device_fwdbwd, 'loop_fwdbwd': loop_fwdbwd}
+        def ordered_fwdbwd():
+            clear()
+            os.environ['SDN_DETERMINISTIC'] = '1'      # read when the backward runs
+            try:
+                device_fwd().backward(g)
+            finally:
+                del os.environ['SDN_DETERMINISTIC']
+
+        forms = {'device_fwd': device_fwd, 'loop_fwd': loop_fwd, 'device_fwdbwd': device_fwdbwd, 'ordered_fwdbwd': ordered_fwdbwd,
+                 'loop_fwdbwd': loop_fwdbwd}
         # the same result first
         d, t = device_fwd(), loop_fwd()
         assert torch.equal(d.view(torch.int32), t.view(torch.int32)), 'the two forms differ forward'
@@ -151,6 +183,12 @@ def main():
         loop_fwdbwd()
         rels = [float((x - m.grad).abs().max() / m.grad.abs().max()) for x, m in zip(gd, maps)]
         assert max(rels) <= 1e-5, rels
+        ordered_fwdbwd()
+        go = [m.grad.clone() for m in maps]
+        ordered_fwdbwd()
+        assert all(torch.equal(x.view(torch.int32), m.grad.view(torch.int32)) for x, m in zip(go, maps)), 'the ordered backward gave other bytes'
+        rels_ordered = [float((x - y).abs().max() / y.abs().max()) for x, y in zip(go, gd)]
+        assert max(rels_ordered) <= 1e-5, rels_ordered
         for fn in forms.values():
             for _ in range(a.warmup):
                 fn()
@@ -158,7 +196,8 @@ def main():
         for _ in range(a.reps):
             for k, fn in forms.items():   # alternating: what disturbs one form disturbs the other
                 samples[k].append(region(fn, a.inner))
-        r = {'pool': pool, 'R': R, 'bytes': counted_bytes(R, pool), 'gradient_max_difference_between_forms': rels}
+        r = {'pool': pool, 'R': R, 'bytes': counted_bytes(R, pool), 'gradient_max_difference_between_forms': rels,
+             'ordered_max_difference_from_atomic': rels_ordered, 'tile_meetings': tile_meetings(boxes[0].cpu().numpy(), pool)}
         for k, v in samples.items():
             r[k + '_ms'] = round(statistics.median(v), 5)
             r[k + '_spread'] = [round(min(v), 5), round(max(v), 5)]
