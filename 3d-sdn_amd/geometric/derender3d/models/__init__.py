@@ -19,6 +19,7 @@ from torch.nn.modules import Module
 import neural_renderer as nr
 
 from derender3d import TargetType
+from derender3d.models import heads
 from derender3d.models.derenderer import Derenderer
 from derender3d.models.renderer import RenderType, Renderer
 from derender3d.models.transforms import FFD, FFDBank, PerspectiveTransform
@@ -79,6 +80,8 @@ class Derenderer3d(Module):
     outputs, pose quantities and (in reproject mode) the rendered silhouette / normal / depth maps; `render(blob)`
     re-renders from a (possibly edited or optimised) blob -- the call sites of geometric/scripts/main.py:443,516."""
 
+    _device_heads = False   # heads.use_device_heads sets it on the instance
+
     def __init__(self, mode, image_size, render_size, objs=None):
         super(Derenderer3d, self).__init__()
         self.mode, self.image_size, self.render_size = mode, image_size, render_size
@@ -122,6 +125,14 @@ class Derenderer3d(Module):
 
     # ------------------------------------------------------------------------------------------------ encoder
     def forward(self, images, roi_norms, focals):
+        if self._device_heads:   # heads.use_device_heads: the roi arithmetic below and the derenderer's heads in the same launches
+            got = heads.device_blob(self.derenderer, images, roi_norms)
+            blob = {'_roi_norms': roi_norms, '_mroi_norms': got.pop('_mroi_norms'), '_droi_norms': got.pop('_droi_norms'),
+                    '_focals': focals}
+            blob.update(got)
+            if self.mode & TargetType.reproject:
+                blob.update(self.render(blob))
+            return blob
         top_left, bottom_right = roi_norms[:, 0:2], roi_norms[:, 2:4]
         blob = {
             '_roi_norms': roi_norms,

@@ -9,6 +9,7 @@ key-compatible ResNet-18.
 import torch
 import torch.nn as nn
 
+from . import heads
 from .resnet import resnet18
 
 # (name, width) of the fixed-width leading columns of the output row; the class and FFD blocks follow
@@ -18,6 +19,7 @@ _FIXED_COLUMNS = (('_theta_deltas', 2), ('_translation2ds', 2), ('_log_scales', 
 class Derenderer(nn.Module):
     in_size = 4        # two normalised rois (mask roi, detection roi) of 2 numbers each
     hidden_size = 256
+    _device_heads = False   # heads.use_device_heads sets it on the instance
 
     def __init__(self, num_classes=8, grid_size=4):
         super().__init__()
@@ -37,6 +39,8 @@ class Derenderer(nn.Module):
         self.fc1, self.fc2, self._fc3 = (nn.Linear(a, b) for a, b in zip(widths[:-1], widths[1:]))
 
     def forward(self, images, mroi_norms, droi_norms):
+        if self._device_heads:   # heads.use_device_heads: everything behind the ResNet's pooling as ops.derender_heads
+            return heads.device_blob(self, images, (mroi_norms, droi_norms))
         h = torch.cat((self.relu(self.net(images)), mroi_norms, droi_norms), dim=1)
         for layer in (self.fc1, self.fc2):
             h = self.relu(layer(h))

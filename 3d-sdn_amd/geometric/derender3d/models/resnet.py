@@ -67,13 +67,18 @@ class ResNet18(nn.Module):
     def forward(self, x):
         """torchvision's ResNet.forward on the HIP kernels (sdn_hip/bnnet.py); `avgpool` is the AdaptiveAvgPool2d(1) the
         Derenderer patches in (derenderer.py:26), `fc` a plain library GEMM."""
+        return self.fc(self.pooled(x))
+
+    def pooled(self, x):
+        """what `forward` hands to `self.fc`: the globally pooled features [n, 512] (the device heads read them directly,
+        derender3d/models/heads.py)"""
         if not isinstance(self.avgpool, nn.AdaptiveAvgPool2d) or self.avgpool.output_size not in (1, (1, 1)):
             raise NotImplementedError('ResNet18 on the HIP path pools to 1x1 (derenderer.py:26)')
         x = hb.max_pool_3x3_s2(hb.batch_norm(self.bn1, hb.conv2d(self.conv1, x), relu=True))
         for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
             for block in layer:
                 x = block(x)
-        return self.fc(hb.global_avg_pool(x))
+        return hb.global_avg_pool(x)
 
 
 def resnet18(pretrained=False):

@@ -151,6 +151,9 @@ def _declare(L):
     _pp = ctypes.POINTER(_vp)
     sig['sdn_rpn_outputs_fwd'] = [_pp, _pp, _ip, _ip, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
     sig['sdn_rpn_outputs_bwd'] = [_vp, _vp, _vp, _vp, _ip, _ip, _ci, _ci, _ci, _pp, _pp, _vp]
+    sig['sdn_derender_heads_workspace_bytes'] = [_ci] * 5 + [ctypes.POINTER(_sz)]
+    sig['sdn_derender_heads_fwd'] = [_vp] * 12 + [_ci] * 5 + [_vp] * 5 + [_vp]
+    sig['sdn_derender_heads_bwd'] = [_vp] * 15 + [_ci] * 5 + [_vp] * 9 + [_vp, _sz, _vp]
     sig['sdn_train_losses_scratch'] = [_ci, _ci, _cl, ctypes.POINTER(_sz)]
     sig['sdn_train_losses_fwd'] = [_vp] * 7 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd, _vp, _vp, _vp]
     sig['sdn_train_losses_bwd'] = [_vp] * 6 + [_cl] + [_vp] * 7 + [_ci, _ci, _ci, _ci, _cd, _cd] + [_vp] * 9 + [_vp]
@@ -189,7 +192,7 @@ def _declare(L):
         try:
             fn = getattr(L, name)
         except AttributeError:
-            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*, sdn_pyramid_roi_align_*, sdn_proposal_layer*, sdn_detection_layer*, sdn_detection_targets*, sdn_rpn_targets*, sdn_training_item*, sdn_rpn_outputs_*, sdn_pyramid_roi_align_bwd_ordered*): a library built before them is stale
+            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*, sdn_pyramid_roi_align_*, sdn_proposal_layer*, sdn_detection_layer*, sdn_detection_targets*, sdn_rpn_targets*, sdn_training_item*, sdn_rpn_outputs_*, sdn_pyramid_roi_align_bwd_ordered*, sdn_derender_heads_*): a library built before them is stale
             raise SdnHipError('%s does not export %s -- rebuild it (`python __graft_entry__.py build`)' % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = _ci
@@ -244,6 +247,7 @@ def exported_symbols():
             'sdn_rpn_targets_workspace_bytes', 'sdn_rpn_targets',
             'sdn_training_item_workspace_bytes', 'sdn_training_item_image', 'sdn_training_item',
             'sdn_rpn_outputs_fwd', 'sdn_rpn_outputs_bwd',
+            'sdn_derender_heads_workspace_bytes', 'sdn_derender_heads_fwd', 'sdn_derender_heads_bwd',
             'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
             'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
             'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',

@@ -2417,6 +2417,165 @@ def rpn_outputs(class_maps, bbox_maps):
     return RpnOutputsFn.apply(*(cls + box))
 
 
+DERENDER_HEADS_MAX_CLASSES, DERENDER_HEADS_MAX_N = 16, 65535   # csrc/derender_heads_check.h: DH_MAX_CLASSES, DH_MAX_N
+DERENDER_HEADS_ROWS, DERENDER_HEADS_SLAB = 16, 128               # DH_ROWS, DH_SLAB
+DERENDER_HEADS_KEYS = ('_theta_deltas', '_translation2ds', '_log_scales', '_log_depths', '_class_probs', '_ffd_coeffs')
+
+_dh_sizes = {}
+
+
+def derender_heads_workspace_bytes(n, F, Hd, classes, coeffs):
+    """bytes of the workspace of sdn_derender_heads_bwd: the library's own answer, remembered per shape"""
+    key = (int(n), int(F), int(Hd), int(classes), int(coeffs))
+    r = _dh_sizes.get(key)
+    if r is None:
+        if len(_dh_sizes) > 256:
+            _dh_sizes.clear()
+        nbytes = ctypes.c_size_t(0)
+        check(lib().sdn_derender_heads_workspace_bytes(*key, ctypes.byref(nbytes)))
+        r = _dh_sizes[key] = nbytes.value
+    return r
+
+
+def _dh_pieces(out, n, classes, coeffs):
+    """the six output groups, contiguous pieces of the one buffer `out` [n * O] (include/sdn_hip.h)"""
+    widths, pieces, at = (2, 2, 3, 1, classes, classes * coeffs), [], 0
+    for w in widths:
+        pieces.append(out[at:at + n * w].view(n, w))
+        at += n * w
+    pieces[5] = pieces[5].view(n, classes, coeffs)
+    return pieces
+
+
+class DerenderHeadsFn(torch.autograd.Function):
+    """The Derenderer's heads (geometric/derender3d/models/derenderer.py:34-56 of the reference, models/__init__.py:70-77) --
+    sdn_derender_heads_fwd / _bwd (include/sdn_hip.h), four launches each way.  Inputs: pooled, roi_norms or None, centre or None,
+    extent or None, the four (weight, bias) pairs flat, the class count.  Returns the six output groups, and with roi_norms the
+    centre and the extent behind them (no gradient).  Only what needs_input_grad asks for is computed; an output that nothing
+    differentiates arrives as None and is not read.  `derender_heads` below checks types and shapes."""
+
+    @staticmethod
+    def forward(ctx, pooled, roi_norms, centre, extent, w0, b0, w1, b1, w2, b2, w3, b3, classes):
+        n, F = pooled.shape
+        Hd, O = w0.shape[0], w3.shape[0]
+        coeffs = (O - 8 - classes) // classes
+        dev = pooled.device
+        with torch.cuda.device(dev):
+            out = torch.empty(n * O, dtype=torch.float32, device=dev)
+            saved = torch.empty(n * (3 * Hd + 1), dtype=torch.float32, device=dev)
+            made = []
+            if roi_norms is not None:
+                centre, extent = (torch.empty(n, 2, dtype=torch.float32, device=dev) for _ in range(2))
+                made = [centre, extent]
+            check(lib().sdn_derender_heads_fwd(ptr(pooled), ptr(roi_norms), None if made else ptr(centre), None if made else ptr(extent),
+                                               ptr(w0), ptr(b0), ptr(w1), ptr(b1), ptr(w2), ptr(b2), ptr(w3), ptr(b3), n, F, Hd, classes,
+                                               coeffs, ptr(out), ptr(made[0]) if made else None, ptr(made[1]) if made else None, None,
+                                               ptr(saved), stream()))
+        ctx.save_for_backward(pooled, centre, extent, w0, w1, w2, w3, out, saved)
+        ctx.sizes = (n, F, Hd, classes, coeffs)
+        ctx.set_materialize_grads(False)
+        if made:
+            ctx.mark_non_differentiable(*made)
+        return tuple(_dh_pieces(out, n, classes, coeffs) + made)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, *grads):
+        need = ctx.needs_input_grad
+        wanted = [need[0]] + list(need[4:12])            # pooled, then w0, b0, .. w3, b3
+        if not any(wanted):
+            return (None,) * 13
+        n, F, Hd, classes, coeffs = ctx.sizes
+        pooled, centre, extent, w0, w1, w2, w3, out, saved = ctx.saved_tensors
+        dev = pooled.device
+        shapes = [(n, F), (Hd, F), (Hd,), (Hd, Hd + 4), (Hd,), (Hd, Hd), (Hd,), tuple(w3.shape), (w3.shape[0],)]
+        with torch.cuda.device(dev):
+            g = [None if t is None else t.to(torch.float32).contiguous() for t in grads[:6]]
+            gin = [torch.empty(shape, dtype=torch.float32, device=dev) if w else None for shape, w in zip(shapes, wanted)]
+            ws = torch.empty(derender_heads_workspace_bytes(n, F, Hd, classes, coeffs), dtype=torch.uint8, device=dev)
+            check(lib().sdn_derender_heads_bwd(*[ptr(t) for t in g], ptr(pooled), ptr(centre), ptr(extent), ptr(w0), ptr(w1), ptr(w2),
+                                               ptr(w3), ptr(out), ptr(saved), n, F, Hd, classes, coeffs, *[ptr(t) for t in gin], ptr(ws),
+                                               ws.numel(), stream()))
+        return (gin[0], None, None, None) + tuple(gin[1:]) + (None,)
+
+
+def _dh_layer(layer, name):
+    """(weight, bias) of an nn.Linear or of a pair"""
+    if isinstance(layer, (tuple, list)) and len(layer) == 2:
+        return layer[0], layer[1]
+    if hasattr(layer, 'weight') and hasattr(layer, 'bias') and layer.bias is not None:
+        return layer.weight, layer.bias
+    raise TypeError('%s must be an nn.Linear with a bias or a (weight, bias) pair, got %r' % (name, type(layer)))
+
+
+def derender_heads(pooled, rois, fc, fc1, fc2, fc3, num_classes):
+    """The blob of Derenderer.forward from the ResNet's pooled features: pooled fp32 [n, F]; rois either roi_norms fp32 [n, 4] (then the
+    blob also holds `_mroi_norms` = (br + tl) / 2 and `_droi_norms` = br - tl, bit-equal to torch) or the pair (centre, extent) of fp32
+    [n, 2]; fc (F -> Hd), fc1 (Hd + 4 -> Hd), fc2 (Hd -> Hd), fc3 (Hd -> 8 + classes + classes * coeffs): nn.Linear modules or
+    (weight, bias) pairs, read in place.  F and Hd multiples of 4, 1 to 16 classes, n up to 65535; n = 0 returns empty tensors without
+    a launch.  Returns `_theta_deltas` [n, 2], `_translation2ds` [n, 2], `_log_scales` [n, 3], `_log_depths` [n, 1], `_class_probs`
+    [n, classes], `_ffd_coeffs` [n, classes, coeffs], pieces of one buffer.  Four launches forward, at most four backward,
+    differentiable in pooled and the eight parameters, the same bits every run; an object's row does not depend on its batch.  A wrong
+    type or dtype raises TypeError, a wrong shape or size, a non-contiguous tensor or a roi tensor that requires a gradient ValueError,
+    a CPU tensor NotImplementedError: there is no torch form."""
+    if isinstance(rois, torch.Tensor):
+        roi_norms, pair, named = rois, None, [('pooled', pooled), ('roi_norms', rois)]
+    elif isinstance(rois, (tuple, list)) and len(rois) == 2:
+        roi_norms, pair, named = None, tuple(rois), [('pooled', pooled), ('centre', rois[0]), ('extent', rois[1])]
+    else:
+        raise TypeError('rois must be roi_norms [n, 4] or the pair (centre, extent), got %r' % type(rois))
+    classes = int(num_classes)
+    layers = []
+    for name, layer in (('fc', fc), ('fc1', fc1), ('fc2', fc2), ('fc3', fc3)):
+        w, b = _dh_layer(layer, name)
+        layers += [(name + '.weight', w), (name + '.bias', b)]
+    named += layers
+    _are_tensors(named)
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+    if pooled.dim() != 2:
+        raise ValueError('pooled must be fp32 [n, F], got %s' % (tuple(pooled.shape),))
+    n, F = pooled.shape
+    if not 1 <= classes <= DERENDER_HEADS_MAX_CLASSES:
+        raise ValueError('%d classes; 1 to %d are supported' % (classes, DERENDER_HEADS_MAX_CLASSES))
+    if n > DERENDER_HEADS_MAX_N:
+        raise ValueError('n %d; up to %d objects are supported' % (n, DERENDER_HEADS_MAX_N))
+    w0, w3 = layers[0][1], layers[6][1]
+    Hd, O = (w0.shape[0], w3.shape[0]) if w0.dim() == 2 and w3.dim() == 2 else (0, 0)
+    if F < 4 or F % 4 or Hd < 4 or Hd % 4:
+        raise ValueError('F %d and Hd %d (fc.weight %s); positive multiples of 4 are supported' % (F, Hd, tuple(w0.shape)))
+    coeffs = (O - 8 - classes) // classes
+    if coeffs < 1 or 8 + classes + classes * coeffs != O:
+        raise ValueError('fc3 has %d outputs; 8 + classes + classes * coeffs with %d classes is supported' % (O, classes))
+    shapes = [(Hd, F), (Hd,), (Hd, Hd + 4), (Hd,), (Hd, Hd), (Hd,), (O, Hd), (O,)]
+    for (name, t), shape in zip(layers, shapes):
+        if tuple(t.shape) != shape:
+            raise ValueError('%s must be %s, got %s' % (name, list(shape), tuple(t.shape)))
+    for name, t in named[1:len(named) - 8]:
+        shape = (n, 4) if roi_norms is not None else (n, 2)
+        if tuple(t.shape) != shape:
+            raise ValueError('%s must be %s, got %s' % (name, list(shape), tuple(t.shape)))
+        if t.requires_grad:
+            raise ValueError('%s requires a gradient; the heads give none to the roi vectors' % name)
+    if max(n * O, n * F, O * Hd, Hd * F) >= 2 ** 31:
+        raise ValueError('n * O, n * F, O * Hd and Hd * F must stay below 2^31')
+    _contiguous(named)
+    _on_one_device(named, 'the derenderer heads only run on the GPU')
+    if n == 0:
+        empty = [pooled.new_empty(0, w) for w in (2, 2, 3, 1, classes)] + [pooled.new_empty(0, classes, coeffs)]
+        blob = dict(zip(DERENDER_HEADS_KEYS, empty))
+        if roi_norms is not None:
+            blob['_mroi_norms'], blob['_droi_norms'] = pooled.new_empty(0, 2), pooled.new_empty(0, 2)
+        return blob
+    centre, extent = pair if pair is not None else (None, None)
+    got = DerenderHeadsFn.apply(pooled, roi_norms, centre, extent, *[t for _name, t in layers], classes)
+    blob = dict(zip(DERENDER_HEADS_KEYS, got[:6]))
+    if roi_norms is not None:
+        blob['_mroi_norms'], blob['_droi_norms'] = got[6], got[7]
+    return blob
+
+
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 

@@ -81,7 +81,8 @@ const char* sdn_last_error(void);
  * sdn_detection_layer_workspace_bytes, sdn_detection_layer added; still 20: sdn_detection_targets_workspace_bytes,
  * sdn_detection_targets added; still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added; still 20: sdn_training_item_workspace_bytes,
  * sdn_training_item_image, sdn_training_item added; still 20: sdn_rpn_outputs_fwd, sdn_rpn_outputs_bwd added; still 20:
- * sdn_pyramid_roi_align_bwd_ordered_workspace_bytes, sdn_pyramid_roi_align_bwd_ordered added -- new entry
+ * sdn_pyramid_roi_align_bwd_ordered_workspace_bytes, sdn_pyramid_roi_align_bwd_ordered added; still 20:
+ * sdn_derender_heads_workspace_bytes, sdn_derender_heads_fwd, sdn_derender_heads_bwd added -- new entry
  * points only, no signature or buffer size of an existing one changed; a library without them fails to bind by name).  A binding must compare sdn_version() with the SDN_ABI_VERSION it was
  * written against and refuse a library that answers otherwise (sdn_hip/__init__.py: lib()): a stale lib/libsdn_hip.so would otherwise be handed buffers of the wrong
  * size. */
@@ -1241,6 +1242,40 @@ int sdn_rpn_outputs_fwd(const float* const* class_maps, const float* const* bbox
                         float* rpn_class_logits, float* rpn_probs, float* rpn_bbox, sdnStream stream);
 int sdn_rpn_outputs_bwd(const float* grad_logits, const float* grad_probs, const float* grad_bbox, const float* rpn_probs, const int* H,
                         const int* W, int L, int k, int B, float* const* grad_class_maps, float* const* grad_bbox_maps, sdnStream stream);
+
+/* The Derenderer's heads (csrc/derender_heads.hip): net.fc, ReLU, the cat with the two roi vectors, fc1, ReLU, fc2, ReLU, _fc3, the
+ * six slices, the pose pair's normalisation and the class softmax -- geometric/derender3d/models/derenderer.py:27-32 (the layers),
+ * :34-43 (the MLP), :45-56 (split, norm :54, softmax :55, view :56) -- and the roi centre / extent arithmetic in front of it,
+ * geometric/derender3d/models/__init__.py:70-77.  fp32 throughout; no atomics, no memset, no host copy, no workgroup waits for
+ * another; every sum's order follows from the widths alone (a weight gradient's walk over the objects: from the object's index), so
+ * the bits are the same every run and object r of a batch gets what it gets alone.
+ * Widths: F (pooled features) and Hd (hidden) positive multiples of 4, classes 1 to 16, coeffs >= 1 per class,
+ * O = 8 + classes + classes * coeffs, n = 1 to 65535 objects; every element count below 2^31.  w0 [Hd, F], w1 [Hd, Hd + 4],
+ * w2 [Hd, Hd], w3 [O, Hd] and their biases: nn.Linear's own tensors, read in place.
+ * _fwd, FOUR launches (one per layer).  pooled fp32 [n, F]; the roi vectors as roi_norms [n, 4] -- then centre = (br + tl) / 2 and
+ * extent = br - tl, bit-equal to torch, are written to centre_out / extent_out [n, 2] -- or as centre and extent [n, 2] (then
+ * centre_out / extent_out are NULL).  out [n * O]: _theta_deltas [n, 2] = row[:, 0:2] / sqrt(r0^2 + r1^2) (a zero pair gives NaN, as
+ * the formula does), _translation2ds [n, 2], _log_scales [n, 3], _log_depths [n, 1], _class_probs [n, classes] = expf(x - max) / sum
+ * (one expf per element; a non-finite logit follows the formula), _ffd_coeffs [n, classes, coeffs], one after the other, each
+ * contiguous.  row (may be NULL): _fc3's own output [n, O].  saved [n * (3 Hd + 1)]: the three post-ReLU activations [n, Hd] and the
+ * pose pair's norm [n], for _bwd.  The weights need 16-byte alignment, everything else 4.
+ * _bwd, at most FOUR launches.  The six output gradients in out's order, any of which may be NULL (not read, no zeros made); pooled,
+ * centre, extent (the forward's centre_out / extent_out in the roi_norms form), the four weights, the forward's out and saved.  It
+ * undoes the normalisation, (g - d (d.g)) / norm, and the softmax, p (g - sum p g), and writes g_pooled [n, F], the four weight and
+ * the four bias gradients, each only if its pointer is given and every element once; what nobody asks for is not computed.
+ * workspace: sdn_derender_heads_workspace_bytes(n, F, Hd, classes, coeffs), 16-byte aligned, not cleared by the caller.
+ * SDN_EINVAL with a message, before any launch, for widths outside these ranges, both roi forms or neither, NULL or misaligned
+ * pointers and a workspace that is too small. */
+int sdn_derender_heads_workspace_bytes(int n, int F, int Hd, int classes, int coeffs, size_t* bytes);
+int sdn_derender_heads_fwd(const float* pooled, const float* roi_norms, const float* centre, const float* extent, const float* w0,
+                           const float* b0, const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
+                           const float* b3, int n, int F, int Hd, int classes, int coeffs, float* out, float* centre_out,
+                           float* extent_out, float* row, float* saved, sdnStream stream);
+int sdn_derender_heads_bwd(const float* g_theta, const float* g_trans, const float* g_scales, const float* g_depths, const float* g_probs,
+                           const float* g_ffd, const float* pooled, const float* centre, const float* extent, const float* w0,
+                           const float* w1, const float* w2, const float* w3, const float* out, const float* saved, int n, int F, int Hd,
+                           int classes, int coeffs, float* g_pooled, float* g_w0, float* g_b0, float* g_w1, float* g_b1, float* g_w2,
+                           float* g_b2, float* g_w3, float* g_b3, void* workspace, size_t workspace_bytes, sdnStream stream);
 
 /* ==== launch lists: one host call per conv-chain pass ===========================================================================
  * In the reference one pass over a network is `self.model(input)` (textural/models/networks.py:238-239, 306-308, 395-407)
