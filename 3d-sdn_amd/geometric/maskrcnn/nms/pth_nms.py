@@ -11,11 +11,9 @@ kernel `dets_temp`, a copy made BEFORE the score sort, so for UNSORTED input its
 `order[keep]` then indexes a different permutation -- a defect that its callers never trigger, not a contract.
 The whole pass (score sort, pair mask, greedy scan) stays on the device: one host read of the kept count at the end, where
 the reference copies the n x n/64 mask to the host.  CPU tensors raise NotImplementedError (no fallback)."""
-import ctypes
-
 import torch
 
-from sdn_hip import check, lib, ptr, stream, want
+from sdn_hip import check, lib, ptr, size_query, stream, want
 
 
 def pth_nms(dets, thresh, strict=True):
@@ -32,9 +30,7 @@ def pth_nms(dets, thresh, strict=True):
     areas = ((boxes[:, 3] - boxes[:, 1] + 1) * (boxes[:, 2] - boxes[:, 0] + 1)).contiguous()
     keep = torch.empty(n, dtype=torch.int64, device=dets.device)
     count = torch.empty(1, dtype=torch.int64, device=dets.device)
-    nbytes = ctypes.c_size_t(0)
-    check(lib().sdn_nms_workspace_bytes(n, ctypes.byref(nbytes)))
-    ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dets.device)
+    ws = torch.empty(size_query(lib().sdn_nms_workspace_bytes, (n,)), dtype=torch.uint8, device=dets.device)
     check(lib().sdn_nms(ptr(boxes), ptr(areas), n, float(thresh), int(bool(strict)), ptr(keep), ptr(count), ptr(ws),
                         ws.numel(), stream()))
     return order[keep[:int(count.item())]].contiguous()

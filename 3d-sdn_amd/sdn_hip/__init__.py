@@ -33,9 +33,9 @@ class SdnHipError(RuntimeError):
     pass
 
 
-def _declare(L):
-    L.sdn_last_error.restype = ctypes.c_char_p
-    L.sdn_version.restype = _ci
+def _signatures():
+    """THE list of entry points: name -> argtypes of every `int sdn_*(...)` of include/sdn_hip.h.  sdn_last_error and sdn_version,
+    the two that do not return an error code, are declared by _declare itself."""
     sig = {
         'sdn_project_vertices': [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp],
         'sdn_project_vertices_bwd': [_vp, _ci, _ci, _ci, _vp, _vp, _vp, _vp, _ci, _vp, _vp, _vp],
@@ -161,11 +161,10 @@ def _declare(L):
     sig['sdn_perspective_transform'] = [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp]
     sig['sdn_perspective_transform_bwd'] = [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                             _vp, _vp, _vp, _vp]
-    _i8pp = _vp
     sig['sdn_bn_forward'] = [_vp, _cl, _ci, _vp, _vp, _vp, _vp, _cf, _cf, _ci, _vp, _ci, _vp, _vp, _vp, _vp, _vp]
     sig['sdn_bn_backward'] = [_vp, _vp, _vp, _vp, _vp, _cl, _ci, _ci, _ci, _vp, _vp, _vp, _vp]
-    sig['sdn_maxpool3x3s2_fwd'] = [_vp, _ci, _ci, _ci, _ci, _vp, _i8pp, _vp]
-    sig['sdn_maxpool3x3s2_bwd'] = [_vp, _i8pp, _ci, _ci, _ci, _ci, _vp, _vp]
+    sig['sdn_maxpool3x3s2_fwd'] = [_vp, _ci, _ci, _ci, _ci, _vp, _vp, _vp]
+    sig['sdn_maxpool3x3s2_bwd'] = [_vp, _vp, _ci, _ci, _ci, _ci, _vp, _vp]
     sig['sdn_avgpool_global'] = [_vp, _ci, _ci, _ci, _vp, _ci, _vp]
     sig['sdn_nms_workspace_bytes'] = [_ci, ctypes.POINTER(_sz)]
     sig['sdn_nms'] = [_vp, _vp, _ci, _cf, _ci, _vp, _vp, _vp, _sz, _vp]
@@ -188,16 +187,24 @@ def _declare(L):
     sig['sdn_program_create'] = [_vp, _ci, _vp, _sz, _ci, ctypes.POINTER(_vp)]
     sig['sdn_program_run'] = [_vp, ctypes.POINTER(_vp), _ci, _vp, _vp, ctypes.POINTER(_cf), ctypes.POINTER(_ci)]
     sig['sdn_program_destroy'] = [_vp]
-    for name, argtypes in sig.items():
+    return sig
+
+
+_SIG = _signatures()
+
+
+def _declare(L):
+    """Set argtypes and restype on the entry points of `L` (the library, or a stand-in of a test or tool); -> the table."""
+    L.sdn_last_error.restype = ctypes.c_char_p
+    L.sdn_version.restype = _ci
+    for name, argtypes in _SIG.items():
         try:
             fn = getattr(L, name)
-        except AttributeError:
-            # entry points added without a revision bump (the sdn_segm_ppm_* family, sdn_encode_maps, sdn_inst_index_*, sdn_mrcnn_loss_*, sdn_pyramid_roi_align_*, sdn_proposal_layer*, sdn_detection_layer*, sdn_detection_targets*, sdn_rpn_targets*, sdn_training_item*, sdn_rpn_outputs_*, sdn_pyramid_roi_align_bwd_ordered*, sdn_derender_heads_*): a library built before them is stale
+        except AttributeError:   # whatever the name: a library without it was built before it was added
             raise SdnHipError('%s does not export %s -- rebuild it (`python __graft_entry__.py build`)' % (LIB_PATH, name))
         fn.argtypes = argtypes
         fn.restype = _ci
-    # optional families (present once the corresponding .hip files are linked in)
-    return sig
+    return _SIG
 
 
 def lib():
@@ -224,35 +231,7 @@ def lib():
 
 def exported_symbols():
     """Names declared in include/sdn_hip.h that this binding expects."""
-    return ['sdn_last_error', 'sdn_version', 'sdn_project_vertices', 'sdn_project_vertices_bwd', 'sdn_gather_faces',
-            'sdn_gather_faces_bwd', 'sdn_face_normals', 'sdn_face_normals_bwd', 'sdn_raster_workspace_bytes',
-            'sdn_rasterize_fwd', 'sdn_raster_work_counters', 'sdn_raster_bwd_workspace_bytes', 'sdn_rasterize_bwd', 'sdn_ffd_decode', 'sdn_ffd_decode_bwd', 'sdn_ffd_coefficients',
-            'sdn_timing_enable', 'sdn_timing_declare_work', 'sdn_timing_read', 'sdn_timing_read_slot', 'sdn_conv_gemm', 'sdn_conv_gemm_phases', 'sdn_conv_gemm_workspace_bytes', 'sdn_conv_wgrad', 'sdn_conv_wgrad_narrow', 'sdn_conv_wgrad_head_mfma', 'sdn_conv_narrow_fwd', 'sdn_conv_head_steps', 'sdn_conv_head_mfma', 'sdn_in_apply', 'sdn_in_bwd',
-            'sdn_act_bwd', 'sdn_reflect_fold', 'sdn_conv_pack_weights', 'sdn_conv_unpack_grad', 'sdn_split_planes', 'sdn_conv_pack_weights_kmajor',
-            'sdn_conv_tile', 'sdn_conv_wgrad_tile', 'sdn_conv_halo', 'sdn_conv_halo_blocks', 'sdn_segment_mean', 'sdn_l1_loss_fwd', 'sdn_l1_loss_bwd', 'sdn_silhouette_loss_fwd', 'sdn_silhouette_loss_bwd', 'sdn_assemble_nhwc', 'sdn_pose_params', 'sdn_pose_algebra', 'sdn_pose_algebra_bwd',
-            'sdn_pose_params_bwd', 'sdn_composite_frame', 'sdn_edit_assemble', 'sdn_scene_cover', 'sdn_scene_crops', 'sdn_scene_edit',
-            'sdn_unmold_masks', 'sdn_scene_gt_masks', 'sdn_scene_paint2d',
-            'sdn_scene_id_workspace_bytes', 'sdn_scene_id_stats', 'sdn_scene_id_planes', 'sdn_assemble_planes', 'sdn_assemble_maps',
-            'sdn_train_rois', 'sdn_train_crops', 'sdn_train_id_stats_workspace_bytes', 'sdn_train_id_stats', 'sdn_train_crops_mixed',
-            'sdn_train_losses_scratch', 'sdn_train_losses_fwd', 'sdn_train_losses_bwd',
-            'sdn_segm_fuse', 'sdn_segm_labels_from_colors', 'sdn_segm_confusion', 'sdn_segm_train_batch', 'sdn_segm_loss_fwd', 'sdn_segm_loss_bwd',
-            'sdn_segm_ppm_pool', 'sdn_segm_ppm_fill', 'sdn_segm_ppm_fill_bwd', 'sdn_segm_ppm_pool_bwd',
-            'sdn_encode_maps', 'sdn_inst_index_workspace_bytes', 'sdn_inst_index_build', 'sdn_inst_index_rank',
-            'sdn_mrcnn_loss_workspace_bytes', 'sdn_mrcnn_loss_fwd', 'sdn_mrcnn_loss_bwd',
-            'sdn_pyramid_roi_align_grad_floats', 'sdn_pyramid_roi_align_fwd', 'sdn_pyramid_roi_align_bwd',
-            'sdn_pyramid_roi_align_bwd_ordered_workspace_bytes', 'sdn_pyramid_roi_align_bwd_ordered',
-            'sdn_proposal_layer_workspace_bytes', 'sdn_proposal_layer',
-            'sdn_detection_layer_workspace_bytes', 'sdn_detection_layer',
-            'sdn_detection_targets_workspace_bytes', 'sdn_detection_targets',
-            'sdn_rpn_targets_workspace_bytes', 'sdn_rpn_targets',
-            'sdn_training_item_workspace_bytes', 'sdn_training_item_image', 'sdn_training_item',
-            'sdn_rpn_outputs_fwd', 'sdn_rpn_outputs_bwd',
-            'sdn_derender_heads_workspace_bytes', 'sdn_derender_heads_fwd', 'sdn_derender_heads_bwd',
-            'sdn_perspective_transform_scratch', 'sdn_perspective_transform', 'sdn_perspective_transform_bwd', 'sdn_bn_forward', 'sdn_bn_backward',
-            'sdn_maxpool3x3s2_fwd', 'sdn_maxpool3x3s2_bwd', 'sdn_avgpool_global', 'sdn_nms_workspace_bytes', 'sdn_nms',
-            'sdn_crop_and_resize_fwd', 'sdn_crop_and_resize_bwd', 'sdn_avgpool3x3s2_fwd', 'sdn_avgpool3x3s2_bwd', 'sdn_render_maps_bytes', 'sdn_render_maps_fwd', 'sdn_raster_phase_clocks',
-            'sdn_render_maps_bwd', 'sdn_program_create', 'sdn_program_run',
-            'sdn_program_destroy']
+    return ['sdn_last_error', 'sdn_version'] + list(_SIG)
 
 
 def deterministic():
@@ -309,44 +288,57 @@ def const_f32(values, device):
     return t
 
 
+def size_query(fn, ints=(), outputs=1):
+    """What a size entry point of the library answers.  `fn` is the function object itself -- the caller writes
+    `lib().sdn_..._bytes`, so that `lib` is looked up in the caller's module --, `ints` its int arguments, handed over as they
+    are (a caller that takes sizes of any kind converts them), `outputs` the number of `size_t *` behind them.  -> an int, or a
+    tuple of `outputs` ints."""
+    out = [_sz(0) for _ in range(outputs)]
+    check(fn(*ints, *[ctypes.byref(n) for n in out]))
+    return out[0].value if outputs == 1 else tuple(n.value for n in out)
+
+
+def c_ints(values):
+    """an `int[len(values)]` of Python ints for a `const int *` parameter"""
+    return (_ci * len(values))(*values)
+
+
+def c_ptrs(tensors):
+    """a `void *[len(tensors)]` of the tensors' addresses, NULL for None"""
+    return (_vp * len(tensors))(*[ptr(t) for t in tensors])
+
+
+def c_floats(values):
+    """a `float[len(values)]` of host numbers"""
+    return (ctypes.c_float * len(values))(*values)
+
+
 def raster_workspace(bs, nf, S, device):
-    n = _sz(0)
-    check(lib().sdn_raster_workspace_bytes(bs, nf, S, ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=device)
+    return torch.empty(size_query(lib().sdn_raster_workspace_bytes, (bs, nf, S)), dtype=torch.uint8, device=device)
 
 
 def perspective_transform_scratch(n, V):
     """(bytes of `key`, bytes of `acc`) of sdn_perspective_transform / _bwd, asked of the library."""
-    kb, ab = _sz(0), _sz(0)
-    check(lib().sdn_perspective_transform_scratch(n, V, ctypes.byref(kb), ctypes.byref(ab)))
-    return kb.value, ab.value
+    return size_query(lib().sdn_perspective_transform_scratch, (n, V), 2)
 
 
 def train_losses_scratch(B, R, nffd):
     """bytes of the `scratch` of sdn_train_losses_fwd / _bwd, asked of the library"""
-    n = _sz(0)
-    check(lib().sdn_train_losses_scratch(B, R, nffd, ctypes.byref(n)))
-    return n.value
+    return size_query(lib().sdn_train_losses_scratch, (B, R, nffd))
 
 
 def raster_bwd_workspace(bs, nf, S, device):
-    n = _sz(0)
-    check(lib().sdn_raster_bwd_workspace_bytes(bs, nf, S, ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=device)
+    return torch.empty(size_query(lib().sdn_raster_bwd_workspace_bytes, (bs, nf, S)), dtype=torch.uint8, device=device)
 
 
 def scene_id_workspace(device):
     """the histograms of sdn_scene_id_stats, sized by the library; the call clears them itself"""
-    n = _sz(0)
-    check(lib().sdn_scene_id_workspace_bytes(ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=device)
+    return torch.empty(size_query(lib().sdn_scene_id_workspace_bytes), dtype=torch.uint8, device=device)
 
 
 def train_id_workspace(B, device):
     """the histograms of sdn_train_id_stats for B items, sized by the library; the call clears them itself"""
-    n = _sz(0)
-    check(lib().sdn_train_id_stats_workspace_bytes(int(B), ctypes.byref(n)))
-    return torch.empty(n.value, dtype=torch.uint8, device=device)
+    return torch.empty(size_query(lib().sdn_train_id_stats_workspace_bytes, (int(B),)), dtype=torch.uint8, device=device)
 
 
 def timing_enable(on=True):

@@ -26,7 +26,7 @@ import weakref
 
 import torch
 
-from . import check, lib, stream
+from . import check, lib, size_query, stream
 from . import deterministic as _deterministic
 from . import convplan as cp
 from . import program as pg
@@ -598,9 +598,7 @@ def _emit_gemm(b, packs, st, which, x_slot, N, IH, IW, Cip, out_slot, OH, OW, Co
     Kp, rows = e.meta
     wsn = 0
     if ws is not None:
-        n = ctypes.c_size_t(0)
-        check(lib().sdn_conv_gemm_workspace_bytes(N, OH, OW, Cop, ctypes.byref(n)))
-        wsn = ws.need(n.value)
+        wsn = ws.need(size_query(lib().sdn_conv_gemm_workspace_bytes, (N, OH, OW, Cop)))
     b.op(pg.OP_CONV_GEMM, buf=[x_slot, out_slot, b.static(e.buf), bias, stats, ws.slot if ws is not None else None],
          i=[N, IH, IW, Cip, OH, OW, Cop, L.QH, L.QW, L.istride, L.ostride, L.py, L.px, len(L.taps), pad_mode, int(in_relu),
             Kp, rows, act, int(accumulate), precision], l=[wsn], taps=L.taps, desc=desc, flops=flops)

@@ -8,19 +8,91 @@ Each Function mirrors one piece of the reference's Chainer graph (paths under
   RasterizeMaps    Rasterize + flip + 2x2 pool       neural_renderer/rasterize.py:19-974
 """
 import ctypes
+import functools
+import threading
 
 import numpy as np
 import torch
 from torch.autograd.function import once_differentiable
 
-from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, check, deterministic, lib, ptr, raster_bwd_workspace,
-               raster_workspace, scene_id_workspace, stream, train_id_workspace, want)
+from . import (AA, ACCUMULATE, ALPHA, COUNT_WORK, DEPTH, FACE_COLOR, K1_COVERAGE, RGB, SAVE_MAPS, SERIAL_EDGES, STREAM_FACES, c_floats, c_ints, c_ptrs, check, const_f32,
+               deterministic, lib, perspective_transform_scratch, ptr, raster_bwd_workspace, raster_workspace, scene_id_workspace, size_query, stream,
+               train_id_workspace, train_losses_scratch, want)
 
 CAMERA_NONE, CAMERA_LOOK, CAMERA_LOOK_AT = 0, 1, 2
 
-import threading
-
 _tls = threading.local()
+
+# a size the library answers for a shape, asked once per shape
+_remembered = functools.lru_cache(maxsize=256)
+
+
+# ---- the checks of the operators that never copy an argument: its type, then its shape (at the call site), then contiguity, then the
+# device.  (The older operators go through want(): a CPU tensor is refused first, a non-contiguous one copied.) ----
+
+def _is_tensor(t, name):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+
+
+def _are_tensors(named):
+    for name, t in named:
+        _is_tensor(t, name)
+
+
+def _count_tensor(t, name):
+    """an optional count that is handed through unread: an int32 [1] tensor; _on_one_device then asks for the device"""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError('%s must be None or an int32 [1] tensor on the device, got %r' % (name, type(t)))
+    if t.dtype != torch.int32:
+        raise TypeError('%s must be %s, got %s' % (name, torch.int32, t.dtype))
+    if t.numel() != 1:
+        raise ValueError('%s must hold one element, got %s' % (name, tuple(t.shape)))
+
+
+def _four_floats(values, name):
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise TypeError('%s must be four host numbers; a tensor on %s would have to be read back' % (name, values.device))
+        values = values.tolist()
+    out = [float(v) for v in values]
+    if len(out) != 4:
+        raise ValueError('%s must hold four values, got %d' % (name, len(out)))
+    return out
+
+
+def _not_contiguous(name, t):
+    return ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
+
+
+def _contiguous(named, fp32=()):
+    """tensor by tensor: float32 where its name is in `fp32`, then contiguous"""
+    for name, t in named:
+        if name in fp32 and t.dtype != torch.float32:
+            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
+        if not t.is_contiguous():
+            raise _not_contiguous(name, t)
+
+
+def _on_gpu(t, name, what):
+    """`what` ends the refusal: 'the ... only runs on the GPU'"""
+    if not t.is_cuda:
+        raise NotImplementedError('%s is on %s; %s' % (name, t.device, what))
+
+
+def _on_device_of(first, dev, named):
+    """every tensor of `named` on `dev`, the device of the argument called `first`"""
+    for name, t in named:
+        if t.device != dev:
+            raise ValueError('%s is on %s, %s on %s' % (name, t.device, first, dev))
+
+
+def _on_one_device(named, what):
+    """tensor by tensor: on the GPU, then on the device of the first"""
+    first, dev = named[0][0], named[0][1].device
+    for name, t in named:
+        _on_gpu(t, name, what)
+        _on_device_of(first, dev, ((name, t),))
 
 
 class verification:
@@ -88,18 +160,10 @@ def _f32(t, name):
     return want(t, torch.float32, name)
 
 
-_ptf_sizes = {}
-
-
+@_remembered
 def _ptf_scratch(n, V):
     """(key bytes, acc bytes) of sdn_perspective_transform / _bwd: the library's own answer, remembered per shape."""
-    r = _ptf_sizes.get((n, V))
-    if r is None:
-        from . import perspective_transform_scratch
-        if len(_ptf_sizes) > 256:
-            _ptf_sizes.clear()
-        r = _ptf_sizes[(n, V)] = perspective_transform_scratch(n, V)
-    return r
+    return perspective_transform_scratch(n, V)
 
 
 class ProjectVertices(torch.autograd.Function):
@@ -247,7 +311,6 @@ class RasterizeMaps(torch.autograd.Function):
             if isinstance(background_color, torch.Tensor):
                 bg = background_color.to(device=dev, dtype=torch.float32).contiguous()
             else:
-                from . import const_f32
                 bg = const_f32(background_color if background_color is not None else (0, 0, 0), dev)
             bg_per_batch = 1 if bg.dim() == 2 else 0
         face_inv = torch.empty((bs, nf, 3, 3), dtype=torch.float32, device=dev)
@@ -266,7 +329,6 @@ class RasterizeMaps(torch.autograd.Function):
                                       bg_per_batch, flags, ptr(face_inv), ptr(fim), ptr(wmap), ptr(dmap),
                                       ptr(rgbmap), ptr(rgb), ptr(alpha), ptr(depth), ptr(ws), ws.numel(), stream()))
         if flags & COUNT_WORK:
-            import ctypes
             c = (ctypes.c_ulonglong * 3)()
             check(lib().sdn_raster_work_counters(ptr(ws), bs, nf, S, c, stream()))
             _tls.last_work = (int(c[0]), int(c[1]), int(c[2]))
@@ -325,8 +387,6 @@ class RenderMapsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, faces_idx, fill_back, camera_mode, eye, direction, up, width, flip_x, image_size,
                 anti_aliasing, near, far, eps, eps_alpha, background_color, want_normal, want_depth):
-        import ctypes
-        from . import const_f32
         v = _f32(vertices, 'vertices')
         f = want(faces_idx, torch.int32, 'faces')
         if v.dim() != 3 or v.shape[2] != 3:
@@ -576,18 +636,10 @@ class SilhouetteLossFn(torch.autograd.Function):
         return gm, None, (gf.reshape(ctx.ffd_shape) if gf is not None else None), None
 
 
-_train_loss_sizes = {}
-
-
+@_remembered
 def _train_losses_scratch(B, R, nffd):
     """bytes of sdn_train_losses_*'s scratch: the library's own answer, remembered per shape"""
-    r = _train_loss_sizes.get((B, R, nffd))
-    if r is None:
-        from . import train_losses_scratch
-        if len(_train_loss_sizes) > 256:
-            _train_loss_sizes.clear()
-        r = _train_loss_sizes[(B, R, nffd)] = train_losses_scratch(B, R, nffd)
-    return r
+    return train_losses_scratch(B, R, nffd)
 
 
 class TrainLossesFn(torch.autograd.Function):
@@ -659,7 +711,6 @@ class PerspectiveTransformFn(torch.autograd.Function):
         fixed = zooms_given is not None
         if fixed:
             zg = _f32(zooms_given, 'zooms').reshape(n)
-            from . import const_f32
             zt = const_f32([1.0] * n, v.device)   # the backward kernels see zoom = key_ratio * 1 (a cached constant: no fill launch)
         else:
             zg = None
@@ -750,7 +801,6 @@ class AvgPool3x3S2Fn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x):
-        import ctypes
         x = want_strided(x, 'input')
         N, C, H, W = x.shape
         OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
@@ -767,7 +817,6 @@ class AvgPool3x3S2Fn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes
         N, C, H, W = ctx.shape
         g = want_strided(g, 'grad')
         if ctx.inner_c:
@@ -870,10 +919,8 @@ def edit_assemble(base_segm, edit_inst, obj_label, obj_pose, code_ids, codes, po
     if pose_channels not in (1, 2):
         raise ValueError('pose_channels must be 1 (binned pose) or 2 (feat_pose_num_bins == 0)')
     dev = edit_inst.device
-    for t, name in ((base_segm, 'base_segm'), (obj_label, 'obj_label'), (obj_pose, 'obj_pose'), (code_ids, 'code_ids'),
-                    (codes, 'codes')):
-        if t.device != dev:
-            raise ValueError('%s is on %s, edit_inst on %s' % (name, t.device, dev))
+    _on_device_of('edit_inst', dev, (('base_segm', base_segm), ('obj_label', obj_label), ('obj_pose', obj_pose), ('code_ids', code_ids),
+                                     ('codes', codes)))
     C, K = codes.shape
     with torch.cuda.device(dev):   # the stream handed over is this device's current one
         segm = torch.empty(F, 1, H, W, dtype=torch.float32, device=dev)
@@ -1025,8 +1072,7 @@ def scene_gt_masks(scene_u8, codes):
         raise ValueError('scene_u8 must be uint8 [H, W, 3], got %s' % (tuple(scene_u8.shape),))
     if codes.dim() != 2 or codes.shape[1] != 3 or codes.shape[0] < 1:
         raise ValueError('codes must be uint8 [K, 3] with K >= 1, got %s' % (tuple(codes.shape),))
-    if codes.device != scene_u8.device:
-        raise ValueError('codes is on %s, scene_u8 on %s' % (codes.device, scene_u8.device))
+    _on_device_of('scene_u8', scene_u8.device, (('codes', codes),))
     H, W, K = scene_u8.shape[0], scene_u8.shape[1], codes.shape[0]
     dev = scene_u8.device
     with torch.cuda.device(dev):
@@ -1047,8 +1093,7 @@ def _id_maps(scene, disparity):
         raise ValueError('scene must be int32 [H, W], got %s' % (tuple(scene.shape),))
     if tuple(disparity.shape) != tuple(scene.shape):
         raise ValueError('disparity must be int32 %s as the scene, got %s' % (tuple(scene.shape), tuple(disparity.shape)))
-    if disparity.device != scene.device:
-        raise ValueError('disparity is on %s, scene on %s' % (disparity.device, scene.device))
+    _on_device_of('scene', scene.device, (('disparity', disparity),))
     return scene, disparity
 
 
@@ -1084,9 +1129,7 @@ def scene_id_planes(scene, disparity, ids, thr, planes=True, ignore_planes=False
     if not (planes or cover):
         raise ValueError('neither planes nor cover asked for')
     dev = scene.device
-    for t, name in ((ids, 'ids'), (thr, 'thr')):
-        if t.device != dev:
-            raise ValueError('%s is on %s, scene on %s' % (name, t.device, dev))
+    _on_device_of('scene', dev, (('ids', ids), ('thr', thr)))
     H, W = scene.shape
     n = ids.shape[0]
     with torch.cuda.device(dev):
@@ -1136,9 +1179,7 @@ def scene_paint2d(cover, n, records_host=None, tables=None, frames=1):
         raise ValueError('records must be [%d, %d, %d], got %s' % (F, N, PAINT2D_REC_INTS, tuple(recs.shape)))
     if bounds.dim() != 2 or bounds.shape[1] != 2 or kk8.dim() != 1:
         raise ValueError('bounds must be [M, 2] and kk8 [K], got %s, %s' % (tuple(bounds.shape), tuple(kk8.shape)))
-    for t, name in ((recs, 'records'), (bounds, 'bounds'), (kk8, 'kk8')):
-        if t.device != dev:
-            raise ValueError('%s is on %s, cover on %s' % (name, t.device, dev))
+    _on_device_of('cover', dev, (('records', recs), ('bounds', bounds), ('kk8', kk8)))
     with torch.cuda.device(dev):
         out = torch.empty(F, 1, H, W, dtype=torch.uint8, device=dev)
         check(lib().sdn_scene_paint2d(ptr(cover), records_host.ctypes.data, ptr(recs), F, N, ptr(bounds), bounds.shape[0],
@@ -1284,8 +1325,7 @@ def train_rois(scenes_u8, items):
         raise ValueError('scenes_u8 must be uint8 [Fr, H, W, 3], got %s' % (tuple(scenes_u8.shape),))
     if items.dim() != 2 or items.shape[1] != 4 or items.shape[0] < 1:
         raise ValueError('items must be int32 [B, 4] with B >= 1, got %s' % (tuple(items.shape),))
-    if items.device != scenes_u8.device:
-        raise ValueError('items is on %s, scenes_u8 on %s' % (items.device, scenes_u8.device))
+    _on_device_of('scenes_u8', scenes_u8.device, (('items', items),))
     Fr, H, W, _ = scenes_u8.shape
     B = items.shape[0]
     with torch.cuda.device(items.device):
@@ -1329,9 +1369,8 @@ def train_crops(frames_u8, scenes_u8, rois_host, objs_host, items_host, tables, 
     if nearer.dim() != 2 or nearer.shape[1] != 3:
         raise ValueError('nearer must be uint8 [total, 3], got %s' % (tuple(nearer.shape),))
     dev = frames_u8.device
-    for t, name in ((scenes_u8, 'scenes_u8'), (objs, 'objs'), (bounds, 'bounds'), (kk8, 'kk8'), (items, 'items'), (nearer, 'nearer')):
-        if t.device != dev:
-            raise ValueError('%s is on %s, frames_u8 on %s' % (name, t.device, dev))
+    _on_device_of('frames_u8', dev, (('scenes_u8', scenes_u8), ('objs', objs), ('bounds', bounds), ('kk8', kk8), ('items', items),
+                                     ('nearer', nearer)))
     with torch.cuda.device(dev):
         images = torch.empty(B, 3, image_size, image_size, device=dev)
         masks = torch.empty(B, 1, mask_size, mask_size, device=dev)
@@ -1396,9 +1435,7 @@ def train_crops_mixed(rois_host, objs_host, items_host, tables, items, nearer, i
     if nearer.dim() != 2 or nearer.shape[1] != 3:
         raise ValueError('nearer must be uint8 [total, 3], got %s' % (tuple(nearer.shape),))
     dev = items.device
-    for t, name in ((objs, 'objs'), (bounds, 'bounds'), (kk8, 'kk8'), (nearer, 'nearer')):
-        if t.device != dev:
-            raise ValueError('%s is on %s, items on %s' % (name, t.device, dev))
+    _on_device_of('items', dev, (('objs', objs), ('bounds', bounds), ('kk8', kk8), ('nearer', nearer)))
     with torch.cuda.device(dev):
         images = torch.empty(B, 3, image_size, image_size, device=dev)
         masks = torch.empty(B, 1, mask_size, mask_size, device=dev) if maps else None
@@ -1461,8 +1498,7 @@ def segm_labels_from_colors(scene_u8, table_host, table):
         raise ValueError('scene_u8 must be uint8 [B, H, W, 3], got %s' % (tuple(scene_u8.shape),))
     if table_host.ndim != 1 or table_host.size % 2 or table_host.size < 2 or tuple(table.shape) != table_host.shape:
         raise ValueError('table_host and table must be int32 [2 K] with K >= 1, got %s, %s' % (table_host.shape, tuple(table.shape)))
-    if table.device != scene_u8.device:
-        raise ValueError('table is on %s, scene_u8 on %s' % (table.device, scene_u8.device))
+    _on_device_of('scene_u8', scene_u8.device, (('table', table),))
     B, H, W = scene_u8.shape[:3]
     dev = scene_u8.device
     with torch.cuda.device(dev):
@@ -1485,8 +1521,7 @@ def segm_confusion(labels, labels_gt, num_class):
     B, _, H, W = labels.shape
     if tuple(labels_gt.shape) != (B, H, W):
         raise ValueError('labels_gt must be int16 [%d, %d, %d], got %s' % (B, H, W, tuple(labels_gt.shape)))
-    if labels_gt.device != labels.device:
-        raise ValueError('labels_gt is on %s, labels on %s' % (labels_gt.device, labels.device))
+    _on_device_of('labels', labels.device, (('labels_gt', labels_gt),))
     C = int(num_class)
     dev = labels.device
     with torch.cuda.device(dev):
@@ -1513,8 +1548,7 @@ def segm_train_batch(frames_u8, scenes_u8, tables_host, Hb, Wb, rate, mean, std)
     if tuple(scenes_u8.shape) != (B, H, W, 3):
         raise ValueError('scenes_u8 must be uint8 [%d, %d, %d, 3], got %s' % (B, H, W, tuple(scenes_u8.shape)))
     dev = frames_u8.device
-    if scenes_u8.device != dev:
-        raise ValueError('scenes_u8 is on %s, frames_u8 on %s' % (scenes_u8.device, dev))
+    _on_device_of('frames_u8', dev, (('scenes_u8', scenes_u8),))
     tables_host = np.ascontiguousarray(tables_host, dtype=np.int32)
     if tables_host.ndim != 1 or tables_host.size < B * SEGM_TRAIN_ITEM_INTS:
         raise ValueError('tables_host must be int32 [n] with n >= %d, got %s' % (B * SEGM_TRAIN_ITEM_INTS, tables_host.shape))
@@ -1589,8 +1623,7 @@ def segm_loss(scores, scores_deepsup, seg_label, deep_sup_scale):
                            (seg_label, 'seg_label', torch.int64)):
         if t is None and name == 'scores_deepsup':
             continue
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+        _is_tensor(t, name)
         if t.dtype != dtype:
             raise TypeError('%s must be %s, got %s' % (name, dtype, t.dtype))
     if scores.dim() != 4:
@@ -1613,9 +1646,7 @@ _MRCNN_INTS = (torch.int32, torch.int64)
 
 def mrcnn_loss_bytes(A, R):
     """(bytes of `workspace`, bytes of `saved`) of sdn_mrcnn_loss_fwd / _bwd, asked of the library"""
-    wb, sb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-    check(lib().sdn_mrcnn_loss_workspace_bytes(int(A), int(R), ctypes.byref(wb), ctypes.byref(sb)))
-    return wb.value, sb.value
+    return size_query(lib().sdn_mrcnn_loss_workspace_bytes, (int(A), int(R)), 2)
 
 
 class MrcnnLossFn(torch.autograd.Function):
@@ -1686,15 +1717,12 @@ def mrcnn_loss(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_clas
              ('target_class_ids', target_class_ids, _MRCNN_INTS), ('mrcnn_class_logits', mrcnn_class_logits, (torch.float32,)),
              ('target_deltas', target_deltas, (torch.float32,)), ('mrcnn_bbox', mrcnn_bbox, (torch.float32,)),
              ('target_mask', target_mask, (torch.float32,)), ('mrcnn_mask', mrcnn_mask, (torch.float32,)))
-    for name, t, _ in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _are_tensors([(name, t) for name, t, _ in named])
     R = target_class_ids.numel()
     for name, t, dtypes in (named if R else named[:4]):
         if t.dtype not in dtypes:
             raise TypeError('%s must be %s, got %s' % (name, ' or '.join(str(d) for d in dtypes), t.dtype))
-        if t.device != rpn_class_logits.device:
-            raise ValueError('%s is on %s, rpn_class_logits on %s' % (name, t.device, rpn_class_logits.device))
+        _on_device_of('rpn_class_logits', rpn_class_logits.device, ((name, t),))
     if rpn_class_logits.dim() != 3 or rpn_class_logits.shape[2] != 2 or rpn_class_logits.shape[1] < 1:
         raise ValueError('rpn_class_logits must be fp32 [1, A, 2], got %s' % (tuple(rpn_class_logits.shape),))
     batch, A = rpn_class_logits.shape[:2]
@@ -1729,15 +1757,12 @@ def mrcnn_loss(rpn_match, rpn_bbox, rpn_class_logits, rpn_pred_bbox, target_clas
 PYRAMID_LEVELS, PYRAMID_MAX_POOL, PYRAMID_CHANNELS = 4, 32, 64   # csrc/pyramid_roi_align_check.h: PRA_LEVELS, PRA_MAX_POOL, PRA_CHANNELS
 
 
-def _pra_ints(values):
-    return (ctypes.c_int * PYRAMID_LEVELS)(*[int(v) for v in values])
-
-
 def pyramid_grad_floats(C, H, W):
     """(float offsets of the four maps' gradients, floats of the one buffer that holds them) of sdn_pyramid_roi_align_bwd, asked of
     the library"""
     offsets, total = (ctypes.c_size_t * PYRAMID_LEVELS)(), ctypes.c_size_t(0)
-    check(lib().sdn_pyramid_roi_align_grad_floats(int(C), _pra_ints(H), _pra_ints(W), offsets, ctypes.byref(total)))
+    four = lambda values: (ctypes.c_int * PYRAMID_LEVELS)(*[int(v) for v in values])   # noqa: E731  (the library reads four of each)
+    check(lib().sdn_pyramid_roi_align_grad_floats(int(C), four(H), four(W), offsets, ctypes.byref(total)))
     return list(offsets), total.value
 
 
@@ -1750,9 +1775,7 @@ def pyramid_backward_path():
 
 def pyramid_ordered_workspace_bytes(R):
     """bytes of the workspace of sdn_pyramid_roi_align_bwd_ordered for R boxes, asked of the library"""
-    n = ctypes.c_size_t(0)
-    check(lib().sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(int(R), ctypes.byref(n)))
-    return n.value
+    return size_query(lib().sdn_pyramid_roi_align_bwd_ordered_workspace_bytes, (int(R),))
 
 
 class PyramidRoiAlignFn(torch.autograd.Function):
@@ -1770,8 +1793,7 @@ class PyramidRoiAlignFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             pooled = torch.empty(R, C, pool, pool, dtype=torch.float32, device=dev)
             levels = torch.empty(R, dtype=torch.int32, device=dev)
-            ptrs = (ctypes.c_void_p * PYRAMID_LEVELS)(*[ptr(m) for m in maps])
-            check(lib().sdn_pyramid_roi_align_fwd(ptr(boxes), R, ptrs, _pra_ints(H), _pra_ints(W), C, pool, image_area, 0.0, ptr(pooled),
+            check(lib().sdn_pyramid_roi_align_fwd(ptr(boxes), R, c_ptrs(maps), c_ints(H), c_ints(W), C, pool, image_area, 0.0, ptr(pooled),
                                                   ptr(levels), stream()))
         ctx.save_for_backward(boxes)
         ctx.sizes = (R, C, H, W, pool, image_area)
@@ -1792,10 +1814,10 @@ class PyramidRoiAlignFn(torch.autograd.Function):
             if pyramid_backward_path() == 'ordered':
                 nbytes = pyramid_ordered_workspace_bytes(R)
                 ws = torch.empty(nbytes, dtype=torch.uint8, device=boxes.device) if nbytes else None   # the caching allocator aligns to 512
-                check(lib().sdn_pyramid_roi_align_bwd_ordered(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf),
+                check(lib().sdn_pyramid_roi_align_bwd_ordered(ptr(g), ptr(boxes), R, c_ints(H), c_ints(W), C, pool, image_area, ptr(buf),
                                                               ptr(ws), nbytes, stream()))
             else:
-                check(lib().sdn_pyramid_roi_align_bwd(ptr(g), ptr(boxes), R, _pra_ints(H), _pra_ints(W), C, pool, image_area, ptr(buf), stream()))
+                check(lib().sdn_pyramid_roi_align_bwd(ptr(g), ptr(boxes), R, c_ints(H), c_ints(W), C, pool, image_area, ptr(buf), stream()))
         views = [buf[o:o + C * h * w].view(C, h, w) if need else None for o, h, w, need in zip(offsets, H, W, ctx.needs_input_grad[1:5])]
         return (None,) + tuple(views) + (None, None)
 
@@ -1816,9 +1838,8 @@ def pyramid_roi_align(boxes, maps, pool, image_area):
     named = [('boxes', boxes)] + [('P%d' % (l + 2), m) for l, m in enumerate(maps)]
     for name, t in named:
         if want(t, torch.float32, name) is not t:       # TypeError / NotImplementedError; a copy means it was not contiguous
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-        if t.device != boxes.device:
-            raise ValueError('%s is on %s, boxes on %s' % (name, t.device, boxes.device))
+            raise _not_contiguous(name, t)
+        _on_device_of('boxes', boxes.device, ((name, t),))
     if boxes.dim() != 2 or boxes.shape[1] != 4:
         raise ValueError('boxes must be fp32 [R, 4], got %s' % (tuple(boxes.shape),))
     for name, m in named[1:]:
@@ -1840,12 +1861,11 @@ PROPOSAL_MAX_PRE_NMS, PROPOSAL_MAX_ANCHORS, PROPOSAL_CHUNK = 8192, 1 << 24, 1024
 
 def proposal_workspace_bytes(A, K, P):
     """bytes of the workspace of sdn_proposal_layer, asked of the library"""
-    return _workspace_bytes(lib().sdn_proposal_layer_workspace_bytes, A, K, P)
+    return size_query(lib().sdn_proposal_layer_workspace_bytes, [int(v) for v in (A, K, P)])
 
 
 def _proposal_rows(t, name, cols):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _is_tensor(t, name)
     if t.dim() == 3:
         if t.shape[0] != 1:
             raise ValueError('%s has batch %d; only 1 is supported, as in the reference ("Currently only supports batchsize 1", '
@@ -1876,8 +1896,7 @@ def proposal_layer(rpn_probs, rpn_bbox, anchors, std_dev, height, width, proposa
     tensor ValueError, a CPU tensor NotImplementedError: there is no torch form."""
     probs = _proposal_rows(rpn_probs, 'rpn_probs', 2)
     deltas = _proposal_rows(rpn_bbox, 'rpn_bbox', 4)
-    if not isinstance(anchors, torch.Tensor):
-        raise TypeError('anchors must be a torch.Tensor, got %r' % (type(anchors),))
+    _is_tensor(anchors, 'anchors')
     if anchors.dim() != 2 or anchors.shape[1] != 4:
         raise ValueError('anchors must be fp32 [A, 4], got %s' % (tuple(anchors.shape),))
     A = anchors.shape[0]
@@ -1912,7 +1931,7 @@ def proposal_layer(rpn_probs, rpn_bbox, anchors, std_dev, height, width, proposa
         count = torch.empty(1, dtype=torch.int32, device=dev)
         rois = torch.empty(P, 4, dtype=torch.float32, device=dev)
         ws = torch.empty(proposal_workspace_bytes(A, K, P), dtype=torch.uint8, device=dev)
-        check(lib().sdn_proposal_layer(ptr(probs.detach()), ptr(deltas.detach()), ptr(anchors.detach()), A, (ctypes.c_float * 4)(*std), height,
+        check(lib().sdn_proposal_layer(ptr(probs.detach()), ptr(deltas.detach()), ptr(anchors.detach()), A, c_floats(std), height,
                                        width, K, P, float(nms_threshold), int(bool(strict)), ptr(order), ptr(boxes_px), ptr(keep), ptr(count),
                                        ptr(rois), ptr(ws), ws.numel(), stream()))
     return order, boxes_px, keep, count, rois
@@ -1923,60 +1942,7 @@ DETECTION_MAX_ROIS, DETECTION_MAX_INSTANCES = 8192, 8192   # csrc/detection_laye
 
 def detection_workspace_bytes(N, C, D):
     """bytes of the workspace of sdn_detection_layer, asked of the library"""
-    return _workspace_bytes(lib().sdn_detection_layer_workspace_bytes, N, C, D)
-
-
-def _four_floats(values, name):
-    if isinstance(values, torch.Tensor):
-        if values.is_cuda:
-            raise TypeError('%s must be four host numbers; a tensor on %s would have to be read back' % (name, values.device))
-        values = values.tolist()
-    out = [float(v) for v in values]
-    if len(out) != 4:
-        raise ValueError('%s must hold four values, got %d' % (name, len(out)))
-    return out
-
-
-def _workspace_bytes(fn, *sizes):
-    """what a *_workspace_bytes entry point of the library answers for these sizes"""
-    n = ctypes.c_size_t(0)
-    check(fn(*[int(v) for v in sizes], ctypes.byref(n)))
-    return n.value
-
-
-def _are_tensors(named):
-    for name, t in named:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
-
-
-def _count_tensor(t, name):
-    """an optional count that is handed through unread: an int32 [1] tensor; _on_one_device then asks for the device"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be None or an int32 [1] tensor on the device, got %r' % (name, type(t)))
-    if t.dtype != torch.int32:
-        raise TypeError('%s must be %s, got %s' % (name, torch.int32, t.dtype))
-    if t.numel() != 1:
-        raise ValueError('%s must hold one element, got %s' % (name, tuple(t.shape)))
-
-
-def _contiguous(named, fp32=()):
-    """tensor by tensor: float32 where its name is in `fp32`, then contiguous"""
-    for name, t in named:
-        if name in fp32 and t.dtype != torch.float32:
-            raise TypeError('%s must be %s, got %s' % (name, torch.float32, t.dtype))
-        if not t.is_contiguous():
-            raise ValueError('%s must be contiguous (strides %s of %s)' % (name, t.stride(), tuple(t.shape)))
-
-
-def _on_one_device(named, what):
-    """every tensor on the GPU and on the device of the first; `what` ends the refusal: 'the ... only runs on the GPU'"""
-    first, dev = named[0][0], named[0][1].device
-    for name, t in named:
-        if not t.is_cuda:
-            raise NotImplementedError('%s is on %s; %s' % (name, t.device, what))
-        if t.device != dev:
-            raise ValueError('%s is on %s, %s on %s' % (name, t.device, first, dev))
+    return size_query(lib().sdn_detection_layer_workspace_bytes, [int(v) for v in (N, C, D)])
 
 
 def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_confidence, nms_threshold, max_instances, roi_count=None,
@@ -2036,8 +2002,8 @@ def detection_layer(rois, probs, deltas, window, std_dev, height, width, min_con
         detections = torch.empty(D, 6, dtype=torch.float32, device=dev)
         boxes_norm = torch.empty(D, 4, dtype=torch.float32, device=dev)
         ws = torch.empty(detection_workspace_bytes(N, C, D), dtype=torch.uint8, device=dev)
-        check(lib().sdn_detection_layer(ptr(rois.detach()), ptr(probs.detach()), ptr(deltas.detach()), N, C, (ctypes.c_float * 4)(*win),
-                                        (ctypes.c_float * 4)(*std), height, width, min_confidence, float(nms_threshold), D, int(bool(strict)),
+        check(lib().sdn_detection_layer(ptr(rois.detach()), ptr(probs.detach()), ptr(deltas.detach()), N, C, c_floats(win),
+                                        c_floats(std), height, width, min_confidence, float(nms_threshold), D, int(bool(strict)),
                                         ptr(roi_count) if roi_count is not None else None, ptr(class_ids), ptr(scores), ptr(boxes_px),
                                         ptr(keep), ptr(count), ptr(detections), ptr(boxes_norm), ptr(ws), ws.numel(), stream()))
     return class_ids, scores, boxes_px, keep, count, detections, boxes_norm
@@ -2049,7 +2015,7 @@ TARGETS_MAX_ROIS, TARGETS_MAX_PER_IMAGE, TARGETS_MAX_BOXES, TARGETS_MAX_MASK_SID
 
 def detection_targets_workspace_bytes(N, G, mask_h, mask_w, R, H, W):
     """bytes of the workspace of sdn_detection_targets, asked of the library"""
-    return _workspace_bytes(lib().sdn_detection_targets_workspace_bytes, N, G, mask_h, mask_w, R, H, W)
+    return size_query(lib().sdn_detection_targets_workspace_bytes, [int(v) for v in (N, G, mask_h, mask_w, R, H, W)])
 
 
 def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_per_image, positive_ratio, std_dev, mask_shape,
@@ -2127,7 +2093,7 @@ def detection_targets(proposals, gt_class_ids, gt_boxes, gt_masks, keys, rois_pe
         ws = torch.empty(detection_targets_workspace_bytes(N, G, mh, mw, R, H, W), dtype=torch.uint8, device=dev)
         check(lib().sdn_detection_targets(ptr(proposals.detach()), ptr(gt_class_ids), ptr(gt_boxes.detach()), ptr(gt_masks.detach()),
                                           ptr(keys.detach()), N, G, mh, mw, int(gt_class_ids.dtype == torch.int64),
-                                          ptr(roi_count) if roi_count is not None else None, R, ratio, (ctypes.c_float * 4)(*std), H, W,
+                                          ptr(roi_count) if roi_count is not None else None, R, ratio, c_floats(std), H, W,
                                           int(bool(use_mini_mask)), ptr(rois), ptr(target_class_ids), ptr(target_deltas), ptr(target_mask),
                                           ptr(rows), ptr(assign), ptr(count), ptr(n_pos), ptr(ws), ws.numel(), stream()))
     return rois, target_class_ids, target_deltas, target_mask, rows, assign, count, n_pos
@@ -2139,7 +2105,7 @@ RPN_TARGETS_MAX_ANCHORS, RPN_TARGETS_MAX_BOXES, RPN_TARGETS_MAX_PER_IMAGE = (1 <
 
 def rpn_targets_workspace_bytes(A, G, T):
     """bytes of the workspace of sdn_rpn_targets, asked of the library"""
-    return _workspace_bytes(lib().sdn_rpn_targets_workspace_bytes, A, G, T)
+    return size_query(lib().sdn_rpn_targets_workspace_bytes, [int(v) for v in (A, G, T)])
 
 
 def rpn_targets(anchors, gt_class_ids, gt_boxes, keys, anchors_per_image, std_dev, gt_count=None):
@@ -2215,7 +2181,7 @@ TRAINING_ITEM_MAX_DIM, TRAINING_ITEM_MAX_MINI, TRAINING_ITEM_MAX_BOXES, TRAINING
 
 def training_item_workspace_bytes(B, H, W, G):
     """bytes of the workspace of sdn_training_item (G >= 1) and sdn_training_item_image (G = 0), asked of the library"""
-    return _workspace_bytes(lib().sdn_training_item_workspace_bytes, B, H, W, G)
+    return size_query(lib().sdn_training_item_workspace_bytes, [int(v) for v in (B, H, W, G)])
 
 
 def _training_item_plan(plan_host, name='plan_host'):
@@ -2325,14 +2291,6 @@ RPN_OUTPUTS_MAX_LEVELS, RPN_OUTPUTS_MAX_K, RPN_OUTPUTS_TILE = 8, 16, 64   # csrc
 RPN_OUTPUTS_MAX_BATCH = 65535                                             # RPO_MAX_BATCH
 
 
-def _rpo_ints(values):
-    return (ctypes.c_int * len(values))(*[int(v) for v in values])
-
-
-def _rpo_ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
-
-
 class RpnOutputsFn(torch.autograd.Function):
     """The tail of RPN.forward on every pyramid level and the three cats of MaskRCNN.predict (geometric/maskrcnn/model.py:896-911,
     :1729-1740) -- sdn_rpn_outputs_fwd / _bwd (include/sdn_hip.h), one launch each way.  Inputs: the L class maps, then the L box maps.
@@ -2351,7 +2309,7 @@ class RpnOutputsFn(torch.autograd.Function):
             logits = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
             probs = torch.empty(B, A, 2, dtype=torch.float32, device=dev)
             bbox = torch.empty(B, A, 4, dtype=torch.float32, device=dev)
-            check(lib().sdn_rpn_outputs_fwd(_rpo_ptrs(cls), _rpo_ptrs(box), _rpo_ints(H), _rpo_ints(W), L, k, B, ptr(logits), ptr(probs),
+            check(lib().sdn_rpn_outputs_fwd(c_ptrs(cls), c_ptrs(box), c_ints(H), c_ints(W), L, k, B, ptr(logits), ptr(probs),
                                             ptr(bbox), stream()))
         ctx.save_for_backward(probs)
         ctx.sizes = (L, k, B, H, W)
@@ -2370,8 +2328,8 @@ class RpnOutputsFn(torch.autograd.Function):
             g_logits, g_probs, g_bbox = [None if g is None else g.to(torch.float32).contiguous() for g in (g_logits, g_probs, g_bbox)]
             g_cls = [torch.empty(B, 2 * k, h, w, dtype=torch.float32, device=dev) for h, w in zip(H, W)]
             g_box = [torch.empty(B, 4 * k, h, w, dtype=torch.float32, device=dev) for h, w in zip(H, W)]
-            check(lib().sdn_rpn_outputs_bwd(ptr(g_logits), ptr(g_probs), ptr(g_bbox), ptr(probs), _rpo_ints(H), _rpo_ints(W), L, k, B,
-                                            _rpo_ptrs(g_cls), _rpo_ptrs(g_box), stream()))
+            check(lib().sdn_rpn_outputs_bwd(ptr(g_logits), ptr(g_probs), ptr(g_bbox), ptr(probs), c_ints(H), c_ints(W), L, k, B,
+                                            c_ptrs(g_cls), c_ptrs(g_box), stream()))
         return tuple(g if need else None for g, need in zip(g_cls + g_box, ctx.needs_input_grad))
 
 
@@ -2421,20 +2379,16 @@ DERENDER_HEADS_MAX_CLASSES, DERENDER_HEADS_MAX_N = 16, 65535   # csrc/derender_h
 DERENDER_HEADS_ROWS, DERENDER_HEADS_SLAB = 16, 128               # DH_ROWS, DH_SLAB
 DERENDER_HEADS_KEYS = ('_theta_deltas', '_translation2ds', '_log_scales', '_log_depths', '_class_probs', '_ffd_coeffs')
 
-_dh_sizes = {}
+
+@_remembered
+def _dh_workspace_bytes(*sizes):
+    """the library's own answer, remembered per shape"""
+    return size_query(lib().sdn_derender_heads_workspace_bytes, sizes)
 
 
 def derender_heads_workspace_bytes(n, F, Hd, classes, coeffs):
     """bytes of the workspace of sdn_derender_heads_bwd: the library's own answer, remembered per shape"""
-    key = (int(n), int(F), int(Hd), int(classes), int(coeffs))
-    r = _dh_sizes.get(key)
-    if r is None:
-        if len(_dh_sizes) > 256:
-            _dh_sizes.clear()
-        nbytes = ctypes.c_size_t(0)
-        check(lib().sdn_derender_heads_workspace_bytes(*key, ctypes.byref(nbytes)))
-        r = _dh_sizes[key] = nbytes.value
-    return r
+    return _dh_workspace_bytes(int(n), int(F), int(Hd), int(classes), int(coeffs))
 
 
 def _dh_pieces(out, n, classes, coeffs):
@@ -2579,14 +2533,6 @@ def derender_heads(pooled, rois, fc, fc1, fc2, fc3, num_classes):
 SEGM_PPM_MAX_SCALES, SEGM_PPM_MAX_SIDE = 4, 8   # csrc/segm_ppm_check.h: PPM_MAX_SCALES, PPM_MAX_SIDE
 
 
-def _ppm_ints(values):
-    return (ctypes.c_int * len(values))(*values)
-
-
-def _ppm_ptrs(tensors):
-    return (ctypes.c_void_p * len(tensors))(*[ptr(t) for t in tensors])
-
-
 class SegmPpmPoolFn(torch.autograd.Function):
     """First half of the pyramid pooling module (semantic/models.py:336-346, 387-397): sdn_segm_ppm_pool forward,
     sdn_segm_ppm_pool_bwd backward, one launch each.  Returns (cat [B, C + sum K, h, w] with conv5 in its first C channels and
@@ -2601,7 +2547,7 @@ class SegmPpmPoolFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             cat = torch.empty(B, C + sum(branch_channels), h, w, dtype=torch.float32, device=dev)
             pooled = torch.empty(B * C * sum(s * s for s in scales), dtype=torch.float32, device=dev)
-            check(lib().sdn_segm_ppm_pool(ptr(x), B, C, h, w, _ppm_ints(scales), _ppm_ints(branch_channels), len(scales), ptr(cat),
+            check(lib().sdn_segm_ppm_pool(ptr(x), B, C, h, w, c_ints(scales), c_ints(branch_channels), len(scales), ptr(cat),
                                           ptr(pooled), stream()))
         ps, at = [], 0
         for s in scales:
@@ -2623,7 +2569,7 @@ class SegmPpmPoolFn(torch.autograd.Function):
             g_cat = None if g_cat is None else g_cat.to(torch.float32).contiguous()
             g_p = [None if g is None else g.to(torch.float32).contiguous() for g in g_p]
             gx = torch.empty(B, C, h, w, dtype=torch.float32, device=dev)
-            check(lib().sdn_segm_ppm_pool_bwd(ptr(g_cat), _ppm_ptrs(g_p), B, C, h, w, _ppm_ints(ctx.scales), _ppm_ints(ctx.channels),
+            check(lib().sdn_segm_ppm_pool_bwd(ptr(g_cat), c_ptrs(g_p), B, C, h, w, c_ints(ctx.scales), c_ints(ctx.channels),
                                               len(ctx.scales), ptr(gx), stream()))
         return gx, None, None
 
@@ -2640,7 +2586,7 @@ class SegmPpmFillFn(torch.autograd.Function):
         B, _, h, w = cat.shape
         scales, channels = [int(y.shape[2]) for y in ys], [int(y.shape[1]) for y in ys]
         with torch.cuda.device(cat.device):
-            check(lib().sdn_segm_ppm_fill(_ppm_ptrs(ys), B, C, h, w, _ppm_ints(scales), _ppm_ints(channels), len(ys), ptr(cat), stream()))
+            check(lib().sdn_segm_ppm_fill(c_ptrs(ys), B, C, h, w, c_ints(scales), c_ints(channels), len(ys), ptr(cat), stream()))
         ctx.mark_dirty(cat)
         ctx.scales, ctx.channels, ctx.C = scales, channels, C
         return cat
@@ -2656,14 +2602,13 @@ class SegmPpmFillFn(torch.autograd.Function):
                 g = g.to(torch.float32).contiguous()
                 gys = [torch.empty(B, K, s, s, dtype=torch.float32, device=g.device) if n else None
                        for n, K, s in zip(need, ctx.channels, ctx.scales)]
-                check(lib().sdn_segm_ppm_fill_bwd(ptr(g), B, ctx.C, h, w, _ppm_ints(ctx.scales), _ppm_ints(ctx.channels), len(need),
-                                                  _ppm_ptrs(gys), stream()))
+                check(lib().sdn_segm_ppm_fill_bwd(ptr(g), B, ctx.C, h, w, c_ints(ctx.scales), c_ints(ctx.channels), len(need),
+                                                  c_ptrs(gys), stream()))
         return (g if ctx.needs_input_grad[0] else None, None) + tuple(gys)
 
 
 def _ppm_tensor(t, name):
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _is_tensor(t, name)
     if t.dtype != torch.float32:
         raise TypeError('%s must be torch.float32, got %s' % (name, t.dtype))
     if t.dim() != 4 or min(t.shape) < 1:
@@ -2690,8 +2635,7 @@ def segm_ppm_pool(conv5, scales, branch_channels):
     B, C, h, w = conv5.shape
     if B * (C + sum(branch_channels)) * h * w >= 2 ** 31:
         raise ValueError('B * (C + sum K) * h * w = %d must stay below 2^31' % (B * (C + sum(branch_channels)) * h * w))
-    if not conv5.is_cuda:
-        raise NotImplementedError('conv5 is on %s; the pyramid pooling kernels only run on the GPU' % (conv5.device,))
+    _on_gpu(conv5, 'conv5', 'the pyramid pooling kernels only run on the GPU')
     return SegmPpmPoolFn.apply(conv5, tuple(scales), tuple(branch_channels))
 
 
@@ -2710,8 +2654,7 @@ def segm_ppm_fill(cat, C, *ys):
     C = int(C)
     devs = [t.device for t in [cat] + ys if isinstance(t, torch.Tensor)]
     for t, name in [(cat, 'cat')] + [(y, 'y[%d]' % k) for k, y in enumerate(ys)]:
-        if not isinstance(t, torch.Tensor):
-            raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+        _is_tensor(t, name)
         if t.dtype != torch.float32:
             raise TypeError('%s must be torch.float32, got %s' % (name, t.dtype))
     B, Ctot, h, w = cat.shape
@@ -2724,8 +2667,7 @@ def segm_ppm_fill(cat, C, *ys):
         raise ValueError('B * Ctot * h * w = %d must stay below 2^31' % (B * Ctot * h * w))
     if any(d != devs[0] for d in devs):
         raise ValueError('cat and the branch outputs are on different devices: %r' % (devs,))
-    if not cat.is_cuda:
-        raise NotImplementedError('cat is on %s; the pyramid pooling kernels only run on the GPU' % (cat.device,))
+    _on_gpu(cat, 'cat', 'the pyramid pooling kernels only run on the GPU')
     if not cat.is_contiguous():
         raise ValueError('cat must be contiguous: it is written in place')
     return SegmPpmFillFn.apply(cat, C, *ys)
@@ -2744,8 +2686,7 @@ ENCODE_POSE_DTYPES = (torch.int32, torch.float32)
 
 def _index_map(t, name, dtypes, like=None):
     """a contiguous [N, 1, H, W] map of one of `dtypes`, of `like`'s shape and device when given"""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError('%s must be a torch.Tensor, got %r' % (name, type(t)))
+    _is_tensor(t, name)
     if t.dtype not in dtypes:
         raise TypeError('%s must be one of %s, got %s' % (name, ', '.join(str(d) for d in dtypes), t.dtype))
     if t.dim() != 4 or t.shape[1] != 1 or min(t.shape) < 1:
@@ -2780,7 +2721,7 @@ def encode_maps(label, inst, pose, label_nc, pose_ch):
     planes = label_nc + (0 if inst is None else 1)
     if N * max(planes, pose_ch) * H * W >= 2 ** 31:
         raise ValueError('N * channels * H * W = %d must stay below 2^31' % (N * max(planes, pose_ch) * H * W))
-    if label.device.type != 'cuda':
+    if label.device.type != 'cuda':   # (the device's type, not is_cuda as _on_gpu asks: kept as it was, so inline)
         raise NotImplementedError('label is on %s; the input encoding kernels only run on the GPU' % (label.device,))
     label = label.contiguous()
     inst = None if inst is None else inst.contiguous()
@@ -2805,9 +2746,7 @@ def inst_index_workspace(device):
     key = (device.index, torch.cuda.current_stream(device).cuda_stream)
     ws = _inst_workspaces.get(key)
     if ws is None:
-        n = ctypes.c_size_t()
-        check(lib().sdn_inst_index_workspace_bytes(ctypes.byref(n)))
-        ws = _inst_workspaces[key] = torch.empty(n.value, dtype=torch.uint8, device=device)
+        ws = _inst_workspaces[key] = torch.empty(size_query(lib().sdn_inst_index_workspace_bytes), dtype=torch.uint8, device=device)
     return ws
 
 
@@ -2821,7 +2760,7 @@ def inst_index(inst, with_counts=False):
     runs on the already disambiguated map.  A wrong type or dtype raises TypeError, a wrong shape or a map that is not contiguous
     ValueError, a CPU tensor NotImplementedError; the library is not touched before."""
     _index_map(inst, 'inst', ENCODE_INST_DTYPES)
-    if inst.device.type != 'cuda':
+    if inst.device.type != 'cuda':   # (as in encode_maps)
         raise NotImplementedError('inst is on %s; the instance numbering kernels only run on the GPU' % (inst.device,))
     if not inst.is_contiguous():
         raise ValueError('inst must be contiguous: it is disambiguated in place')

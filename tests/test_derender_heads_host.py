@@ -6,14 +6,13 @@ import copy
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import derender_heads_util as u
+import host_checks
 import makefile_rules
 from derender3d.models import heads          # the feature itself: without it this module does not import
 from sdn_hip import ops
@@ -25,28 +24,14 @@ CSRC = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    assert int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1)) == 20 == sdn_hip.ABI_VERSION == sdn_hip.lib().sdn_version()
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     clause = 'still 20: sdn_derender_heads_workspace_bytes, sdn_derender_heads_fwd, sdn_derender_heads_bwd added'
     assert clause in history[at - 3000:at]
     assert history.index('sdn_pyramid_roi_align_bwd_ordered added') < history.index(clause) < at
     for line in ('derenderer.py:27-32', ':34-43', ':45-56', 'models/__init__.py:70-77'):      # the reference lines the entry points replace
-        assert line in src, line
-    assert 'sdn_derender_heads_*' in open(os.path.join(ROOT, '3d-sdn_amd', 'sdn_hip', '__init__.py')).read()   # the stale-library comment
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_derender_heads_bwd':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_derender_heads_bwd -- rebuild'):
-        sdn_hip._declare(Stale())
+        assert line in history, line
+    host_checks.stale_library_is_refused(NAMES)        # added without a revision bump: a library built before them is stale
 
 
 def test_the_kernel_file_is_built_exactly_and_keeps_the_contract():
@@ -72,10 +57,7 @@ def test_the_kernel_file_is_built_exactly_and_keeps_the_contract():
 
 
 def test_the_constants_are_mirrored():
-    hdr = open(os.path.join(CSRC, 'derender_heads_check.h')).read()
-
-    def const(name):
-        return int(re.search(r'constexpr int %s = (\d+);' % name, hdr).group(1))
+    const = lambda name: host_checks.constexpr_int('derender_heads_check.h', name)   # noqa: E731
     assert ops.DERENDER_HEADS_MAX_CLASSES == const('DH_MAX_CLASSES') == 16 and ops.DERENDER_HEADS_MAX_N == const('DH_MAX_N') == 65535
     assert ops.DERENDER_HEADS_ROWS == const('DH_ROWS') == 16 and ops.DERENDER_HEADS_SLAB == const('DH_SLAB') == 128
     assert const('DH_FIXED') == 8 == sum(w for _k, w in __import__('derender3d.models.derenderer', fromlist=['x'])._FIXED_COLUMNS)
@@ -227,20 +209,9 @@ def test_the_wrapper_refuses_what_the_kernels_cannot_take():
 def test_the_headers_layouts_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/derender_heads_check.cpp: a stand-alone program with its own main that includes only csrc/derender_heads_check.h; host code
     on the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'derender_heads_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['derender_heads_check.h'] and 'int main()' in text and 'hip' not in text.lower()
     assert re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'derender_heads_check.h')).read()) == ['check_common.h']
-    exe = str(tmp_path / 'derender_heads_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + CSRC, src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the validators' in run.stdout
+    rc, out = host_checks.run_check_program('derender_heads_check', ['derender_heads_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the validators' in out
 
 
 # ---- the model ------------------------------------------------------------------------------------------------------------------------

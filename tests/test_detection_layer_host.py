@@ -7,14 +7,13 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import detection_layer_util as u
+import host_checks
 import makefile_rules
 from maskrcnn import detection_layer as dl   # the feature itself: without it this module does not import
 from maskrcnn import detections as det
@@ -127,26 +126,12 @@ def test_unmold_boxes_reads_the_padded_detections_as_the_unpadded_ones(gold):
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     clause = 'still 20: sdn_detection_layer_workspace_bytes, sdn_detection_layer added'
     assert history.index('sdn_proposal_layer added') < history.index(clause) < at
-    assert 'model.py:744-837' in src and ':731-741' in src
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_detection_layer':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_detection_layer'):
-        sdn_hip._declare(Stale())
+    assert 'model.py:744-837' in history and ':731-741' in history
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_pair_test_and_the_clamp():
@@ -189,7 +174,7 @@ def test_the_constants_are_mirrored_and_the_workspace_comes_from_the_library():
     hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'detection_layer_check.h')).read()
     assert 'DET_MAX_ROIS = PROP_MAX_PRE_NMS' in hdr and 'DET_MAX_INSTANCES = PROP_MAX_PRE_NMS' in hdr
     assert ops.DETECTION_MAX_ROIS == u.MAX_ROIS == ops.PROPOSAL_MAX_PRE_NMS == 8192 and ops.DETECTION_MAX_INSTANCES == u.MAX_INSTANCES == 8192
-    head = int(re.search(r'constexpr int DET_HEAD_INTS = (\d+);', hdr).group(1))
+    head = host_checks.constexpr_int('detection_layer_check.h', 'DET_HEAD_INTS')
 
     def want(N):
         r16 = lambda n: (n + 15) // 16 * 16   # noqa: E731
@@ -348,16 +333,5 @@ def test_the_public_names_and_the_docstrings():
 def test_the_headers_layout_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/detection_layer_check.cpp: a stand-alone program with its own main that includes only csrc/detection_layer_check.h; host
     code on the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'detection_layer_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['detection_layer_check.h'] and 'int main()' in text and 'hip' not in text.lower()
-    exe = str(tmp_path / 'detection_layer_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the validators' in run.stdout
+    rc, out = host_checks.run_check_program('detection_layer_check', ['detection_layer_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the validators' in out

@@ -6,8 +6,6 @@ touched, and the C entry points validate on the host."""
 import ctypes
 import os
 import re
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 import torch
 
 import encode_input_util as u
+import host_checks
 import makefile_rules
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -94,46 +93,22 @@ def test_the_emulated_bitmap_and_rank_scheme_equals_numpys_unique(name):
 def test_the_headers_arithmetic_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/encode_input_check.cpp: a stand-alone program with its own main that includes only csrc/encode_input_check.h; host
     code on the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'encode_input_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['encode_input_check.h'] and 'int main()' in text and 'hip' not in text.lower().replace('.hip', '')
-    exe = str(tmp_path / 'encode_input_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout
+    rc, out = host_checks.run_check_program('encode_input_check', ['encode_input_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out
 
 
 # ---- names ---------------------------------------------------------------------------------------------------------------------------
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     assert all(name in history[history.index('#define SDN_ABI_VERSION') - 3000:history.index('#define SDN_ABI_VERSION')] for name in NAMES)
-    assert 'pix2pixHD_model.py:124-166' in src and 'networks.py:310-325' in src
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_inst_index_rank':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_inst_index_rank'):
-        sdn_hip._declare(Stale())
+    assert 'pix2pixHD_model.py:124-166' in history and 'networks.py:310-325' in history
+    host_checks.stale_library_is_refused(NAMES)
+    import sdn_hip
     from sdn_hip import ops
     n = ctypes.c_size_t()
     assert sdn_hip.lib().sdn_inst_index_workspace_bytes(ctypes.byref(n)) == 0 and n.value == 2 * 65536 * 4 + 16
     assert ops.INST_HEAD_AT == 65536 * 4 and (ops.INST_KEY_MIN, ops.INST_KEY_BITS) == (u.KEY_MIN, u.KEY_BITS)
-    assert (ops.MAP_U8, ops.MAP_I16, ops.MAP_I32, ops.MAP_F32) == tuple(int(re.search(r'#define SDN_MAP_%s (\d)' % k, src).group(1))
+    assert (ops.MAP_U8, ops.MAP_I16, ops.MAP_I32, ops.MAP_F32) == tuple(int(re.search(r'#define SDN_MAP_%s (\d)' % k, history).group(1))
                                                                         for k in ('U8', 'I16', 'I32', 'F32'))
 
 

@@ -5,19 +5,16 @@ sdn_mrcnn_loss_fwd / _bwd and of the binding, all of which run before any launch
 in a stand-alone host program."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import makefile_rules
 import mrcnn_loss_util as u
 from maskrcnn import losses   # the feature itself: without it this module does not import
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ('sdn_mrcnn_loss_workspace_bytes', 'sdn_mrcnn_loss_fwd', 'sdn_mrcnn_loss_bwd')
 
 
@@ -99,26 +96,12 @@ def test_what_the_reference_leaves_undefined_is_left_out_and_counted():
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     assert all(name in history[at - 3000:at] for name in NAMES)
     assert 'still 20: sdn_mrcnn_loss_workspace_bytes, sdn_mrcnn_loss_fwd, sdn_mrcnn_loss_bwd added' in history
-    assert 'model.py:1004-1147' in src and ':1955' in src
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_mrcnn_loss_bwd':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_mrcnn_loss_bwd'):
-        sdn_hip._declare(Stale())
+    assert 'model.py:1004-1147' in history and ':1955' in history
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernels_are_built_without_fma_contraction():
@@ -127,8 +110,7 @@ def test_the_kernels_are_built_without_fma_contraction():
 
 def test_the_constants_are_mirrored_and_the_sizes_come_from_the_library():
     from sdn_hip import ops
-    hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'mrcnn_loss_check.h')).read()
-    const = lambda k: int(eval(re.search(r'constexpr int %s = ([^;]+);' % k, hdr).group(1), {}))   # noqa: E731
+    const = lambda k: host_checks.constexpr_int('mrcnn_loss_check.h', k)   # noqa: E731
     assert const('MRL_THREADS') == 64 and const('MRL_QUAD') == u.QUAD and const('MRL_STEPS') * u.STEP == u.CHUNK == ops.MRCNN_LOSS_CHUNK
     assert const('MRL_MAX_CLASSES') == ops.MRCNN_MAX_CLASSES == 128 and const('MRL_MAX_ANCHORS') == ops.MRCNN_MAX_ANCHORS
     wb, sb = ops.mrcnn_loss_bytes(5003, 13)
@@ -268,16 +250,5 @@ def test_the_public_names_and_the_docstring():
 def test_the_headers_arithmetic_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/mrcnn_loss_check.cpp: a stand-alone program with its own main that includes only csrc/mrcnn_loss_check.h; host code on
     the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'mrcnn_loss_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['mrcnn_loss_check.h'] and 'int main()' in text and 'hip' not in text.lower().replace('.hip', '')
-    exe = str(tmp_path / 'mrcnn_loss_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout
+    rc, out = host_checks.run_check_program('mrcnn_loss_check', ['mrcnn_loss_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out

@@ -8,13 +8,12 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import makefile_rules
 import proposal_layer_util as u
 from maskrcnn import proposals   # the feature itself: without it this module does not import
@@ -110,27 +109,13 @@ def test_the_fixture_holds_what_the_cases_are_there_for(gold):
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     clause = 'still 20: sdn_proposal_layer_workspace_bytes, sdn_proposal_layer added'
     assert clause in history[at - 3000:at]
     assert history.index('sdn_pyramid_roi_align_bwd added') < history.index(clause) < at
-    assert 'model.py:344-407' in src and ':307-328' in src and ':331-341' in src and 'Nothing is differentiable' in history
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_proposal_layer':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_proposal_layer'):
-        sdn_hip._declare(Stale())
+    assert 'model.py:344-407' in history and ':307-328' in history and ':331-341' in history and 'Nothing is differentiable' in history
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_nms_pair_test():
@@ -151,8 +136,7 @@ def test_the_kernels_are_built_without_fma_contraction_and_share_the_nms_pair_te
 
 def test_the_constants_are_mirrored_and_the_workspace_comes_from_the_library():
     from sdn_hip import ops
-    hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'proposal_layer_check.h')).read()
-    const = lambda k: int(eval(re.search(r'constexpr int %s = ([^;]+);' % k, hdr).group(1), {}))   # noqa: E731
+    const = lambda k: host_checks.constexpr_int('proposal_layer_check.h', k)   # noqa: E731
     assert const('PROP_MAX_PRE_NMS') == ops.PROPOSAL_MAX_PRE_NMS == u.MAX_PRE_NMS == 8192
     assert const('PROP_MAX_ANCHORS') == ops.PROPOSAL_MAX_ANCHORS == u.MAX_ANCHORS == 1 << 24
     assert const('PROP_CHUNK') == ops.PROPOSAL_CHUNK == u.CHUNK == 4 * const('PROP_THREADS') and const('PROP_THREADS') % 64 == 0
@@ -302,16 +286,5 @@ def test_the_public_names_and_the_docstrings():
 def test_the_headers_image_network_layout_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/proposal_layer_check.cpp: a stand-alone program with its own main that includes only csrc/proposal_layer_check.h; host
     code on the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'proposal_layer_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['proposal_layer_check.h'] and 'int main()' in text and 'hip' not in text.lower()
-    exe = str(tmp_path / 'proposal_layer_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the validators' in run.stdout
+    rc, out = host_checks.run_check_program('proposal_layer_check', ['proposal_layer_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the validators' in out

@@ -8,13 +8,12 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import pyramid_ordered_util as o
 import pyramid_roi_align_util as u
 
@@ -92,27 +91,12 @@ def test_the_restatement_is_within_the_fixtures_gate_of_its_float64_gradients(go
 
 
 def test_header_binding_and_library_hold_the_new_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    assert int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1)) == 20 == sdn_hip.ABI_VERSION == sdn_hip.lib().sdn_version()
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     clause = 'still 20: sdn_pyramid_roi_align_bwd_ordered_workspace_bytes, sdn_pyramid_roi_align_bwd_ordered added'
     assert clause in history and history.index('sdn_rpn_outputs_bwd added') < history.index(clause) < at
-    assert 'NOT bit-reproducible' in src and 'ORDERED backward' in src and 'crop_and_resize.c:241-247' in src
-    init = open(os.path.join(ROOT, '3d-sdn_amd', 'sdn_hip', '__init__.py')).read()
-    assert 'sdn_pyramid_roi_align_bwd_ordered*' in init        # the stale-library comment
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_pyramid_roi_align_bwd_ordered':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_pyramid_roi_align_bwd_ordered -- rebuild'):
-        sdn_hip._declare(Stale())
+    assert 'NOT bit-reproducible' in history and 'ORDERED backward' in history and 'crop_and_resize.c:241-247' in history
+    host_checks.stale_library_is_refused(NAMES)        # added without a revision bump: a library built before them is stale
     text = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'pyramid_roi_align.hip')).read()
     body = text[text.index('void k_pra_box_records'):text.index('static PraParams pra_params')]
     assert 'tomicAdd' not in body and 'hipMemset' not in text        # no atomics in the ordered kernels, no memset anywhere
@@ -173,8 +157,7 @@ def test_the_workspace_query_answers_and_refuses():
     assert 'sdn_pyramid_roi_align_bwd_ordered_workspace_bytes: bad sizes: R -1' in L.sdn_last_error().decode()
     assert L.sdn_pyramid_roi_align_bwd_ordered_workspace_bytes(5, None) == -1
     assert 'sdn_pyramid_roi_align_bwd_ordered_workspace_bytes: bytes is NULL' in L.sdn_last_error().decode()
-    hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'pyramid_roi_align_check.h')).read()
-    const = lambda k: int(re.search(r'constexpr int %s = (\d+);' % k, hdr).group(1))   # noqa: E731
+    const = lambda k: host_checks.constexpr_int('pyramid_roi_align_check.h', k)   # noqa: E731
     assert const('PRA_RECORD_BYTES') == RECORD_BYTES and const('PRA_TILE') == o.TILE and const('PRA_THREADS') == o.LIST_BATCH
 
 
@@ -210,16 +193,5 @@ def test_the_backward_path_follows_the_switches(monkeypatch):
 def test_the_ordered_validator_and_workspace_size_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/pyramid_roi_align_ordered_check.cpp: a stand-alone program with its own main that includes only
     csrc/pyramid_roi_align_check.h; host code on the CPU in its own process, never loaded into Python, nothing preloaded"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'pyramid_roi_align_ordered_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['pyramid_roi_align_check.h'] and 'int main()' in text and 'hip' not in text.lower()
-    exe = str(tmp_path / 'pyramid_roi_align_ordered_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the ordered validator' in run.stdout
+    rc, out = host_checks.run_check_program('pyramid_roi_align_ordered_check', ['pyramid_roi_align_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the ordered validator' in out

@@ -7,13 +7,12 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import makefile_rules
 import pyramid_roi_align_util as u
 from maskrcnn import pyramid   # the feature itself: without it this module does not import
@@ -95,28 +94,14 @@ def test_no_stored_box_sits_near_a_level_boundary(gold):
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     assert all(name in history[at - 3000:at] for name in NAMES)
     clause = 'still 20: sdn_pyramid_roi_align_grad_floats, sdn_pyramid_roi_align_fwd, sdn_pyramid_roi_align_bwd added'
     assert clause in history
     assert history.index('sdn_mrcnn_loss_bwd added') < history.index(clause) < at
-    assert 'model.py:414-502' in src and ':95-100' in src and 'NOT bit-reproducible' in src and 'gives level 2' in src
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_pyramid_roi_align_bwd':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_pyramid_roi_align_bwd'):
-        sdn_hip._declare(Stale())
+    assert 'model.py:414-502' in history and ':95-100' in history and 'NOT bit-reproducible' in history and 'gives level 2' in history
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernels_are_built_without_fma_contraction_and_share_the_crops_sample():
@@ -133,8 +118,7 @@ def test_the_kernels_are_built_without_fma_contraction_and_share_the_crops_sampl
 
 def test_the_constants_are_mirrored_and_the_layout_comes_from_the_library():
     from sdn_hip import ops
-    hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'pyramid_roi_align_check.h')).read()
-    const = lambda k: int(eval(re.search(r'constexpr int %s = ([^;]+);' % k, hdr).group(1), {}))   # noqa: E731
+    const = lambda k: host_checks.constexpr_int('pyramid_roi_align_check.h', k)   # noqa: E731
     assert const('PRA_LEVELS') == ops.PYRAMID_LEVELS == u.LEVELS == 4
     assert const('PRA_MAX_POOL') == ops.PYRAMID_MAX_POOL == u.MAX_POOL and const('PRA_CHANNELS') == ops.PYRAMID_CHANNELS == u.CHANNELS
     assert const('PRA_THREADS') % 64 == 0 and const('PRA_MAX_POOL') ** 2 * const('PRA_SAMPLE_BYTES') <= 64 * 1024
@@ -270,16 +254,5 @@ def test_the_public_names_and_the_docstrings():
 def test_the_headers_layout_level_rule_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/pyramid_roi_align_check.cpp: a stand-alone program with its own main that includes only
     csrc/pyramid_roi_align_check.h; host code on the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'pyramid_roi_align_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['pyramid_roi_align_check.h'] and 'int main()' in text and 'hip' not in text.lower()
-    exe = str(tmp_path / 'pyramid_roi_align_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the validators' in run.stdout
+    rc, out = host_checks.run_check_program('pyramid_roi_align_check', ['pyramid_roi_align_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the validators' in out

@@ -7,14 +7,13 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
 import detection_layer_util as dlu
+import host_checks
 import makefile_rules
 import predict_util as u
 import proposal_layer_util as plu
@@ -28,26 +27,12 @@ CSRC = os.path.join(ROOT, '3d-sdn_amd', 'csrc')
 
 
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == sdn_hip.ABI_VERSION == sdn_hip.lib().sdn_version()
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     assert history.index('sdn_training_item added') < history.index('sdn_rpn_outputs_fwd, sdn_rpn_outputs_bwd added') < at
     for line in ('model.py:896-911', ':897-899', ':909-911', ':1729-1740'):       # the reference lines the entry points replace
-        assert line in src, line
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_rpn_outputs_bwd':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_rpn_outputs_bwd'):
-        sdn_hip._declare(Stale())
+        assert line in history, line
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernel_file_is_built_like_its_neighbours_and_uses_no_atomics():
@@ -62,10 +47,7 @@ def test_the_kernel_file_is_built_like_its_neighbours_and_uses_no_atomics():
 
 
 def test_the_constants_are_mirrored():
-    hdr = open(os.path.join(CSRC, 'rpn_outputs_check.h')).read()
-
-    def const(name):
-        return int(re.search(r'constexpr int %s = (\d+);' % name, hdr).group(1))
+    const = lambda name: host_checks.constexpr_int('rpn_outputs_check.h', name)   # noqa: E731
     assert ops.RPN_OUTPUTS_MAX_LEVELS == const('RPO_MAX_LEVELS') == 8 and ops.RPN_OUTPUTS_MAX_K == const('RPO_MAX_K') == 16
     assert ops.RPN_OUTPUTS_TILE == const('RPO_TILE') == 64 and ops.RPN_OUTPUTS_MAX_BATCH == const('RPO_MAX_BATCH') == 65535
 
@@ -210,22 +192,11 @@ def test_the_public_names_and_the_docstrings():
 def test_the_headers_table_and_validators_walk_clean_under_asan_and_ubsan(tmp_path):
     """tools/rpn_outputs_check.cpp: a stand-alone program with its own main that includes only csrc/rpn_outputs_check.h; host code on
     the CPU, never loaded into Python"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'rpn_outputs_check.cpp')
-    text = open(src).read()
-    assert re.findall(r'#include "([^"]+)"', text) == ['rpn_outputs_check.h'] and 'int main()' in text and 'hip' not in text.lower()
     # the header stands alone: no other operation's header, only the macros every check header shares (plain C++ as well)
     assert re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'rpn_outputs_check.h')).read()) == ['check_common.h']
     assert not re.findall(r'#include "([^"]+)"', open(os.path.join(CSRC, 'check_common.h')).read())
-    exe = str(tmp_path / 'rpn_outputs_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + CSRC, src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    print(run.stdout.decode())
-    assert run.returncode == 0 and b' 0 failures' in run.stdout and b'the validators' in run.stdout
+    rc, out = host_checks.run_check_program('rpn_outputs_check', ['rpn_outputs_check.h'], tmp_path)
+    assert rc == 0 and b' 0 failures' in out and b'the validators' in out
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------

@@ -7,13 +7,12 @@ import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import makefile_rules
 import rpn_targets_util as u
 from maskrcnn import rpn_targets as rt   # the feature itself: without it this module does not import
@@ -42,16 +41,8 @@ def results():
 @pytest.fixture(scope='module')
 def check_program(tmp_path_factory):
     """tools/rpn_targets_check.cpp built with ASan and UBSan and run once as a child process: (return code, output)"""
-    cxx = shutil.which('g++') or shutil.which('c++') or shutil.which('clang++')
-    assert cxx, 'no host C++ compiler'
-    src = os.path.join(ROOT, 'tools', 'rpn_targets_check.cpp')
-    exe = str(tmp_path_factory.mktemp('rt') / 'rpn_targets_check')
-    # the sanitizers' runtimes are linked into the program itself, so it runs the same whatever the environment preloads
-    static = ['-static-libasan', '-static-libubsan'] if 'clang' not in os.path.basename(cxx) else ['-static-libsan']
-    subprocess.check_call([cxx, '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all'] + static +
-                          ['-I' + os.path.join(ROOT, '3d-sdn_amd', 'csrc'), src, '-o', exe])
-    run = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
-    return run.returncode, run.stdout.decode()
+    rc, out = host_checks.run_check_program('rpn_targets_check', ['rpn_targets_check.h'], tmp_path_factory.mktemp('rt'))
+    return rc, out.decode()
 
 
 @pytest.mark.parametrize('name', list(u.CASES))
@@ -170,26 +161,12 @@ def test_the_check_program_walks_clean_under_asan_and_ubsan(check_program):
 
 # ---- header, binding, library, build -------------------------------------------------------------------------------------------------------
 def test_header_binding_and_library_hold_the_entry_points():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert header == 20 and sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    for name in NAMES:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(NAMES)
     at = history.index('#define SDN_ABI_VERSION')
     clause = 'still 20: sdn_rpn_targets_workspace_bytes, sdn_rpn_targets added'
     assert history.index('sdn_detection_targets added') < history.index(clause) < at
-    assert 'model.py:1214-1322' in src and 'utils.py:52-89' in src
-
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_rpn_targets':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_rpn_targets'):
-        sdn_hip._declare(Stale())
+    assert 'model.py:1214-1322' in history and 'utils.py:52-89' in history
+    host_checks.stale_library_is_refused(NAMES)
 
 
 def test_the_kernels_are_built_exactly_and_use_no_shortcut():

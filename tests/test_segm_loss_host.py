@@ -2,12 +2,12 @@
 float64 expressions of tests/segm_loss_util.py, the ABI revision, the build list, and the argument checks of sdn_segm_loss_fwd /
 _bwd and of the binding, all of which run before any launch."""
 import os
-import re
 
 import numpy as np
 import pytest
 import torch
 
+import host_checks
 import makefile_rules
 import segm_loss_util as u
 
@@ -65,13 +65,7 @@ def test_the_fixture_holds_what_the_cases_are_there_for(gold):
 
 
 def test_the_abi_revision_is_20_everywhere():
-    import sdn_hip
-    src = open(os.path.join(ROOT, 'include', 'sdn_hip.h')).read()
-    assert int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1)) == 20
-    assert sdn_hip.ABI_VERSION == 20 and sdn_hip.lib().sdn_version() == 20
-    assert '20: sdn_segm_loss_fwd' in re.sub(r'\s*\n \*\s*', ' ', src)
-    for name in ('sdn_segm_loss_fwd', 'sdn_segm_loss_bwd'):
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
+    assert '20: sdn_segm_loss_fwd' in host_checks.entry_points(('sdn_segm_loss_fwd', 'sdn_segm_loss_bwd'))
 
 
 def test_the_kernels_are_built_without_fma_contraction():
@@ -81,8 +75,8 @@ def test_the_kernels_are_built_without_fma_contraction():
 def test_the_block_constant_is_mirrored():
     from sdn_hip import ops
     hdr = open(os.path.join(ROOT, '3d-sdn_amd', 'csrc', 'segm_loss_check.h')).read()
-    assert int(re.search(r'constexpr int SGL_PIXELS = (\d+);', hdr).group(1)) == ops.SEGM_LOSS_PIXELS == u.BLOCK_PIXELS
-    assert int(re.search(r'constexpr int SGL_PART_BYTES = (\d+);', hdr).group(1)) == ops.SEGM_LOSS_PART_BYTES
+    assert host_checks.constexpr_int('segm_loss_check.h', 'SGL_PIXELS') == ops.SEGM_LOSS_PIXELS == u.BLOCK_PIXELS
+    assert host_checks.constexpr_int('segm_loss_check.h', 'SGL_PART_BYTES') == ops.SEGM_LOSS_PART_BYTES
     assert 'segm_tail_check.h' in hdr and 'SEG_MAX_CLASSES' in hdr and ops.SEGM_MAX_CLASSES == 32   # one class limit, reused
 
 

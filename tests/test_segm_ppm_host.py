@@ -10,6 +10,7 @@ import torch
 from torch import nn
 from torch.nn import functional as F
 
+import host_checks
 import makefile_rules
 import segm_ppm_util as u
 
@@ -176,29 +177,12 @@ def test_the_c_entry_points_validate_on_the_host():
 
 
 def test_header_binding_and_library_hold_the_ppm_entry_points(monkeypatch):
-    import os
-    import re
-    import sdn_hip
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = open(os.path.join(root, 'include', 'sdn_hip.h')).read()
-    header = int(re.search(r'#define\s+SDN_ABI_VERSION\s+(\d+)', src).group(1))
-    assert sdn_hip.ABI_VERSION == header and sdn_hip.lib().sdn_version() == header
     names = ('sdn_segm_ppm_pool', 'sdn_segm_ppm_fill', 'sdn_segm_ppm_fill_bwd', 'sdn_segm_ppm_pool_bwd')
-    for name in names:
-        assert name in sdn_hip.exported_symbols() and hasattr(sdn_hip.lib(), name)
-        assert re.search(r'\bint %s\(' % name, src)
-    history = re.sub(r'\s*\n \*\s*', ' ', src)
+    history = host_checks.entry_points(names)
     assert all(name in history[history.index('#define SDN_ABI_VERSION') - 3000:history.index('#define SDN_ABI_VERSION')] for name in names)
-    assert 'models.py:336-346, 387-397' in src
-
+    assert 'models.py:336-346, 387-397' in history
     # the family came without a revision bump: a library that lacks one of its entry points is refused by name when it is bound
-    class Stale:
-        def __getattr__(self, name):
-            if name == 'sdn_segm_ppm_fill':
-                raise AttributeError(name)
-            return getattr(sdn_hip.lib(), name)
-    with pytest.raises(sdn_hip.SdnHipError, match='does not export sdn_segm_ppm_fill'):
-        sdn_hip._declare(Stale())
+    host_checks.stale_library_is_refused(names)
 
 
 def test_the_kernels_are_built_without_fma_contraction():
