@@ -1,4 +1,4 @@
-// Device helpers shared by the kernels of libsdn_hip.so: the 64-lane wave reductions, the 8-bit clip, the partial quad store and
+// Device helpers shared by the kernels of libsdn_hip.so: the 64-lane wave reductions, the 8-bit clip, the packed colour of a scene pixel, the partial quad store and
 // the NaN-first min / max.  HIP only: the *_check.h headers are plain C++ and never include this file (check_common.h is theirs).
 #pragma once
 
@@ -75,6 +75,9 @@ __device__ __forceinline__ int wave_exclusive_sum(int v, int lane, int& total)
 
 // ---- scalars ---------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+// the packed colour r | g << 8 | b << 16 of the three bytes at s (a pixel of a scene image, a row of a code table)
+__device__ __forceinline__ int code24(const uint8_t* s) { return (int)s[0] | ((int)s[1] << 8) | ((int)s[2] << 16); }
 
 // torch.max / torch.min of two tensors, np.maximum / np.minimum / np.amax: a NaN on either side is the result
 template <typename T>

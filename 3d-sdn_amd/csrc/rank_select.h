@@ -1,4 +1,7 @@
-// The rank search of the exact radix selects (scene_ids.hip per id of one frame, train_hybrid.hip per item of a batch).
+// The rank search over a 256-bin histogram.  The exact radix select of the disparity percentile calls it from k_ids_select and
+// k_ids_pick (scene_ids.hip), which serve both sdn_scene_id_stats (a row per id of one frame) and sdn_train_id_stats (a row per
+// item of a batch): those kernels live in that one source, so each is defined once in the library, and this header holds no
+// kernel.  The top-k selects of proposal_layer.hip and rpn_targets.hip call it too.
 #pragma once
 
 #include <hip/hip_runtime.h>

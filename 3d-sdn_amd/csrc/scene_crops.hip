@@ -220,12 +220,6 @@ __global__ __launch_bounds__(256) void k_scene_edit(const float* __restrict__ th
     o_int[i] = keep;
 }
 
-static bool debug_checks()
-{
-    const char* e = getenv("SDN_DEBUG_CHECKS");
-    return e && !strcmp(e, "1");
-}
-
 }  // namespace sdn
 
 using namespace sdn;
@@ -237,21 +231,14 @@ SDN_API int sdn_scene_cover(const float* masks, int N, int H, int W, uint32_t* c
     const long HW = (long)H * W;
     const int chunks = (N + 31) / 32;
     hipStream_t st = (hipStream_t)stream;
-    int* flag = nullptr;
-    if (debug_checks()) {
-        if (hipMalloc(&flag, sizeof(int)) != hipSuccess || hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess)
-            return fail(SDN_ELAUNCH, "sdn_scene_cover: no memory for the debug check");
-    }
-    hipLaunchKernelGGL(k_scene_cover, dim3(cdiv(HW, 256), (unsigned)chunks), dim3(256), 0, st, masks, N, HW, cover, flag);
-    int rc = check_launch("k_scene_cover");
-    if (flag) {
-        int bad = 0;
-        hipError_t e = hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(flag);
-        if (e != hipSuccess) return fail(SDN_ELAUNCH, "sdn_scene_cover: debug check: %s", hipGetErrorString(e));
-        if (rc == SDN_OK && bad) return fail(SDN_EINVAL, "sdn_scene_cover: %d mask values are neither 0 nor 1 (binary masks only)", bad);
-    }
+    const auto launch = [&](int* flag) {   // flag: where the kernel counts the values that are neither 0 nor 1, or NULL
+        hipLaunchKernelGGL(k_scene_cover, dim3(cdiv(HW, 256), (unsigned)chunks), dim3(256), 0, st, masks, N, HW, cover, flag);
+        return check_launch("k_scene_cover");
+    };
+    if (!debug_checks()) return launch(nullptr);
+    int bad = 0, rc = SDN_OK;
+    if (int e = debug_count("sdn_scene_cover", st, &bad, [&](int* flag) { rc = launch(flag); })) return e;
+    if (rc == SDN_OK && bad) return fail(SDN_EINVAL, "sdn_scene_cover: %d mask values are neither 0 nor 1 (binary masks only)", bad);
     return rc;
 }
 

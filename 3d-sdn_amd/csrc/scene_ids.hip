@@ -20,12 +20,18 @@
 //                        writer per word, no memset in front.
 // The interpolation between lo and hi stays on the host (derender3d.scene.percentile95_threshold): it is float64 arithmetic
 // whose rounding decides pixels, and the host reads the table anyway to choose the largest masks.
+//
+//   sdn_train_id_stats   CityscapesSemantics.__getitem__ (datasets.py:938-955) for B items over several frames: the same table
+//                        per ITEM (one id of one frame) instead of per id of one frame.  It is the same select: k_ids_init,
+//                        k_ids_select and k_ids_pick, the workspace layout and the launch chain (ids_chain) are the ones above
+//                        over B rows.  Only the two pixel passes are its own:
+//     k_tid_pass_a   blockIdx.y is the item: its one 256-bin histogram lives in the workgroup's LDS, no slots
+//     k_tid_pass_b   the same for the low-byte histograms
+//                        The id and disparity maps are 4-byte elements: the lanes of a wave read consecutive pixels, one dword each.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 
 #include "device_common.h"
 #include "rank_select.h"
@@ -38,26 +44,29 @@ constexpr int ID_COLS = 8;                         // area, y0, x0, y1, x1, n, l
 constexpr int ID_BINS = 256;
 constexpr int ID_THREADS = 256;
 constexpr int ID_ITERS = 8;                        // pixels per thread
-constexpr int ID_CHUNK = ID_THREADS * ID_ITERS;    // pixels per workgroup, consecutive
-constexpr int ID_SLOTS = 16;                       // objects a workgroup aggregates in LDS; further ones add to global memory
-// the workspace, in ints: high-byte histograms [1000][256], the select records [1000][4] (bin and residual rank of i, of i + 1),
-// low-byte histograms [1000][2][256]
-constexpr size_t ID_WS_HI = 0;
-constexpr size_t ID_WS_SEL = ID_WS_HI + (size_t)ID_OBJS * ID_BINS;
-constexpr size_t ID_WS_LO = ID_WS_SEL + (size_t)ID_OBJS * 4;
-constexpr size_t ID_WS_INTS = ID_WS_LO + (size_t)ID_OBJS * 2 * ID_BINS;
+constexpr int ID_CHUNK = ID_THREADS * ID_ITERS;    // pixels of one pass of a workgroup, consecutive
+constexpr int ID_SLOTS = 16;                       // objects a workgroup of k_ids_pass_a / _b aggregates in LDS; further ones add to global memory
+// the workspace of a select over `rows` table rows, in ints: high-byte histograms [rows][256], the select records [rows][4]
+// (bin and residual rank of i, of i + 1), low-byte histograms [rows][2][256]
+constexpr size_t ID_WS_PER_ROW = ID_BINS + 4 + 2 * ID_BINS;
 static_assert(ID_THREADS == ID_BINS, "a workgroup flushes one bin per thread");
 static_assert((ID_SLOTS & (ID_SLOTS - 1)) == 0, "slots are probed modulo a power of two");
 
-__global__ __launch_bounds__(256) void k_ids_init(int32_t* table, int32_t* ws)
+__global__ __launch_bounds__(256) void k_ids_init(int32_t* table, int32_t* ws, int rows)
 {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < ID_WS_INTS) ws[i] = 0;
-    if (i < (size_t)ID_OBJS * ID_COLS) {
+    if (i < (size_t)rows * ID_WS_PER_ROW) ws[i] = 0;
+    if (i < (size_t)rows * ID_COLS) {
         const int c = (int)(i & 7);
         table[i] = (c == 1 || c == 2) ? INT_MAX : 0;   // the invalid roi of sdn_scene_gt_masks
     }
 }
+
+// bin and low byte of a disparity; the masks keep a value outside 0 .. 65535 (a broken precondition) in bounds
+__device__ __forceinline__ int ids_bin(int d) { return (d >> 8) & (ID_BINS - 1); }
+__device__ __forceinline__ int ids_low(int d) { return d & (ID_BINS - 1); }
+// which of the two low-byte histograms of the select record a bin feeds, -1: neither (rec.z == rec.x: one serves both ranks)
+__device__ __forceinline__ int ids_which(int bin, const int4& rec) { return bin == rec.x ? 0 : (bin == rec.z ? 1 : -1); }
 
 __global__ __launch_bounds__(256) void k_ids_range(const int32_t* __restrict__ disparity, long HW, int* bad)
 {
@@ -130,7 +139,9 @@ __global__ __launch_bounds__(ID_THREADS) void k_ids_pass_a(const int32_t* __rest
         if (!rem) continue;
         const unsigned p = (unsigned)(p0 + (long)it * ID_THREADS);   // H W fits an int (the launcher checked)
         const int y = (int)(p / (unsigned)W), x = (int)(p - (unsigned)y * (unsigned)W);
-        const int bin = (d >> 8) & (ID_BINS - 1);   // the mask keeps a value outside 0 .. 65535 (a broken precondition) in bounds
+        // ids_bin(d), written out here and in pass B: through the helpers the compiler allocates this kernel 51 VGPRs for 78, and
+        // the chain of the timing frame took 76 to 78 us for 70 to 72 (profiles/loader_bodies.md)
+        const int bin = (d >> 8) & (ID_BINS - 1);
         while (rem) {   // one round per distinct object among the wave's 64 pixels
             const int src = __ffsll((long long)rem) - 1;
             const int j0 = __shfl(j, src, 64);
@@ -233,8 +244,8 @@ __global__ __launch_bounds__(ID_THREADS) void k_ids_pass_b(const int32_t* __rest
             slot = __shfl(slot, src, 64);
             const int4 rec = reinterpret_cast<const int4*>(sel)[j0];
             if (mine) {   // the low bytes inside a bin are spread: every pixel adds for itself
-                const int bin = (d >> 8) & (ID_BINS - 1), low = d & (ID_BINS - 1);
-                const int w = bin == rec.x ? 0 : (bin == rec.z ? 1 : -1);   // rec.z == rec.x: one histogram serves both ranks
+                const int bin = (d >> 8) & (ID_BINS - 1), low = d & (ID_BINS - 1);   // ids_bin, ids_low, ids_which, written out as in pass A
+                const int w = bin == rec.x ? 0 : (bin == rec.z ? 1 : -1);
                 if (w >= 0) {
                     if (slot >= 0) atomicAdd(&s_lo[slot][w][low], 1);
                     else atomicAdd(hist_lo + ((size_t)j0 * 2 + w) * ID_BINS + low, 1);
@@ -264,6 +275,114 @@ __global__ __launch_bounds__(64) void k_ids_pick(int32_t* table, const int32_t* 
     if (lane == 0) {
         table[ID_COLS * j + 6] = (rec.x << 8) | b_lo;
         table[ID_COLS * j + 7] = (rec.z << 8) | b_hi;
+    }
+}
+
+// ---- the pixel passes of sdn_train_id_stats: B (frame, id) items ----------------------------------------------------------------
+constexpr int TID_ITEM_INTS = 8;
+
+struct IdItem {   // one row of the item table, 8 ints
+    uint64_t ids;          // address of the int32 [H, W] id map
+    uint64_t disparity;    // address of the int32 [H, W] disparity map, or 0
+    int H, W;
+    int id;
+    int pad;
+};
+static_assert(sizeof(IdItem) == TID_ITEM_INTS * sizeof(int32_t), "id item row");
+
+__global__ __launch_bounds__(ID_THREADS) void k_tid_range(const IdItem* __restrict__ items, int* bad)
+{
+    const IdItem it = items[blockIdx.y];
+    const int32_t* disp = reinterpret_cast<const int32_t*>(it.disparity);
+    if (!disp || it.H < 1 || it.W < 1) return;
+    const long HW = (long)it.H * it.W;
+    for (long p = (long)blockIdx.x * ID_THREADS + threadIdx.x; p < HW; p += (long)gridDim.x * ID_THREADS)
+        if (disp[p] < 0 || disp[p] > 65535) atomicAdd(bad, 1);
+}
+
+// blockIdx.y is the item; a workgroup walks the chunks blockIdx.x, blockIdx.x + gridDim.x, ... of its frame.  Thread t holds
+// the pixels chunk + k 256 + t: the lanes of a wave are 64 neighbours, which mostly share the high byte of their disparity:
+// they are grouped by ballot on equal bins and a group adds once into the LDS histogram.
+__global__ __launch_bounds__(ID_THREADS) void k_tid_pass_a(const IdItem* __restrict__ items, int32_t* table, int32_t* hist_hi)
+{
+    __shared__ int s_hist[ID_BINS];
+    __shared__ int s_stat[6];
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
+    const IdItem it = items[b];
+    const int32_t* ids = reinterpret_cast<const int32_t*>(it.ids);
+    const int32_t* disp = reinterpret_cast<const int32_t*>(it.disparity);
+    if (!ids || it.H < 1 || it.W < 1) return;   // uniform over the workgroup; the row stays empty
+    const long HW = (long)it.H * it.W;
+    if ((long)blockIdx.x * ID_CHUNK >= HW) return;
+    s_hist[tid] = 0;
+    if (tid == 0) {
+        s_stat[0] = 0; s_stat[1] = INT_MAX; s_stat[2] = INT_MAX; s_stat[3] = 0; s_stat[4] = 0; s_stat[5] = 0;
+    }
+    __syncthreads();
+    int area = 0, ymin = INT_MAX, xmin = INT_MAX, ymax = -1, xmax = -1, n = 0;
+    for (long c0 = (long)blockIdx.x * ID_CHUNK; c0 < HW; c0 += (long)gridDim.x * ID_CHUNK) {   // uniform over the workgroup
+        for (int k = 0; k < ID_ITERS; k++) {
+            const long p = c0 + (long)k * ID_THREADS + tid;
+            const bool mine = p < HW && ids[p] == it.id;
+            const int d = (mine && disp) ? disp[p] : 0;
+            if (mine) {
+                const unsigned up = (unsigned)p;   // H W fits an int (the launcher's max_pixels; the host checks)
+                const int y = (int)(up / (unsigned)it.W), x = (int)(up - (unsigned)y * (unsigned)it.W);
+                ymin = min(ymin, y); xmin = min(xmin, x); ymax = max(ymax, y); xmax = max(xmax, x);
+                area++;
+            }
+            const bool nz = mine && d != 0;
+            n += nz ? 1 : 0;
+            const int bin = ids_bin(d);
+            unsigned long long left = __ballot(nz);
+            while (left) {   // one round per distinct high byte among the wave's 64 pixels
+                const int src = __ffsll((long long)left) - 1;
+                const int b0 = __shfl(bin, src, 64);
+                const unsigned long long mb = __ballot(nz && bin == b0);
+                left &= ~mb;
+                if (lane == src) atomicAdd(&s_hist[b0], __popcll(mb));
+            }
+        }
+    }
+    area = wave_sum(area);
+    n = wave_sum(n);
+    ymin = wave_imin(ymin); xmin = wave_imin(xmin); ymax = wave_imax(ymax); xmax = wave_imax(xmax);
+    if (lane == 0 && area) ids_note(s_stat, area, ymin, xmin, ymax + 1, xmax + 1, n);
+    __syncthreads();
+    if (!s_stat[0]) return;   // uniform: no pixel of the item in this workgroup's chunks
+    if (tid == 0) ids_note(table + ID_COLS * (size_t)b, s_stat[0], s_stat[1], s_stat[2], s_stat[3], s_stat[4], s_stat[5]);
+    const int c = s_hist[tid];
+    if (c) atomicAdd(hist_hi + (size_t)b * ID_BINS + tid, c);
+}
+
+__global__ __launch_bounds__(ID_THREADS) void k_tid_pass_b(const IdItem* __restrict__ items, const int32_t* __restrict__ sel,
+                                                           int32_t* hist_lo)
+{
+    __shared__ int s_lo[2][ID_BINS];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const IdItem it = items[b];
+    const int32_t* ids = reinterpret_cast<const int32_t*>(it.ids);
+    const int32_t* disp = reinterpret_cast<const int32_t*>(it.disparity);
+    const int4 rec = reinterpret_cast<const int4*>(sel)[b];
+    if (!ids || !disp || it.H < 1 || it.W < 1 || rec.x < 0) return;   // uniform; rec.x < 0: n == 0
+    const long HW = (long)it.H * it.W;
+    if ((long)blockIdx.x * ID_CHUNK >= HW) return;
+    s_lo[0][tid] = 0;
+    s_lo[1][tid] = 0;
+    __syncthreads();
+    for (long c0 = (long)blockIdx.x * ID_CHUNK; c0 < HW; c0 += (long)gridDim.x * ID_CHUNK)
+        for (int k = 0; k < ID_ITERS; k++) {
+            const long p = c0 + (long)k * ID_THREADS + tid;
+            if (p >= HW || ids[p] != it.id) continue;
+            const int d = disp[p];
+            if (d == 0) continue;
+            const int w = ids_which(ids_bin(d), rec);
+            if (w >= 0) atomicAdd(&s_lo[w][ids_low(d)], 1);   // the low bytes inside a bin are spread: every pixel adds for itself
+        }
+    __syncthreads();
+    for (int w = 0; w < 2; w++) {
+        const int c = s_lo[w][tid];
+        if (c) atomicAdd(hist_lo + ((size_t)b * 2 + w) * ID_BINS + tid, c);
     }
 }
 
@@ -315,10 +434,23 @@ __global__ __launch_bounds__(256) void k_ids_planes(const int32_t* __restrict__ 
     store_quad(base, e0, lo, hi, vals);
 }
 
-static bool ids_debug_checks()
+// The chain of five launches of a select over `rows` table rows.  pass_a(hist_hi) and pass_b(sel, hist_lo) issue the caller's
+// pixel passes and return check_launch's answer.
+template <class PassA, class PassB>
+static int ids_chain(int rows, int32_t* table, int32_t* ws, hipStream_t st, PassA pass_a, PassB pass_b)
 {
-    const char* e = getenv("SDN_DEBUG_CHECKS");
-    return e && !strcmp(e, "1");
+    int32_t* hi = ws;
+    int32_t* sel = hi + (size_t)rows * ID_BINS;
+    int32_t* lo = sel + (size_t)rows * 4;
+    hipLaunchKernelGGL(k_ids_init, dim3(cdiv((long)(rows * ID_WS_PER_ROW), 256)), dim3(256), 0, st, table, ws, rows);
+    int rc = check_launch("k_ids_init");
+    if (rc != SDN_OK) return rc;
+    if ((rc = pass_a(hi)) != SDN_OK) return rc;
+    hipLaunchKernelGGL(k_ids_select, dim3(rows), dim3(64), 0, st, table, hi, sel);
+    if ((rc = check_launch("k_ids_select")) != SDN_OK) return rc;
+    if ((rc = pass_b(sel, lo)) != SDN_OK) return rc;
+    hipLaunchKernelGGL(k_ids_pick, dim3(rows), dim3(64), 0, st, table, sel, lo);
+    return check_launch("k_ids_pick");
 }
 
 }  // namespace sdn
@@ -328,7 +460,7 @@ using namespace sdn;
 SDN_API int sdn_scene_id_workspace_bytes(size_t* out)
 {
     if (!out) return fail(SDN_EINVAL, "sdn_scene_id_workspace_bytes: null pointer");
-    *out = ID_WS_INTS * sizeof(int32_t);
+    *out = ID_OBJS * ID_WS_PER_ROW * sizeof(int32_t);
     return SDN_OK;
 }
 
@@ -343,32 +475,61 @@ SDN_API int sdn_scene_id_stats(const int32_t* scene, const int32_t* disparity, i
         return fail(SDN_EINVAL, "sdn_scene_id_stats: the workspace must be aligned to 16 bytes and the table to 4");
     const long HW = (long)H * W;
     hipStream_t st = (hipStream_t)stream;
-    int32_t* ws = static_cast<int32_t*>(workspace);
-    if (ids_debug_checks()) {   // the precondition 0 .. 65535; synchronous
-        int* flag = nullptr;
+    if (debug_checks()) {   // the precondition 0 .. 65535; synchronous
         int bad = 0;
-        if (hipMalloc(&flag, sizeof(int)) != hipSuccess || hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess)
-            return fail(SDN_ELAUNCH, "sdn_scene_id_stats: no memory for the debug check");
-        hipLaunchKernelGGL(k_ids_range, dim3(cdiv(HW, 256)), dim3(256), 0, st, disparity, HW, flag);
-        hipError_t e = hipMemcpyAsync(&bad, flag, sizeof(int), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        (void)hipFree(flag);
-        if (e != hipSuccess) return fail(SDN_ELAUNCH, "sdn_scene_id_stats: debug check: %s", hipGetErrorString(e));
+        if (int rc = debug_count("sdn_scene_id_stats", st, &bad, [&](int* flag) {
+                hipLaunchKernelGGL(k_ids_range, dim3(cdiv(HW, 256)), dim3(256), 0, st, disparity, HW, flag);
+            }))
+            return rc;
         if (bad) return fail(SDN_EINVAL, "sdn_scene_id_stats: %d disparity values lie outside 0 .. 65535 (16-bit maps only)", bad);
     }
     const unsigned first = (unsigned)category * ID_OBJS;
     const unsigned chunks = cdiv(HW, ID_CHUNK);
-    hipLaunchKernelGGL(k_ids_init, dim3(cdiv((long)ID_WS_INTS, 256)), dim3(256), 0, st, table, ws);
-    int rc = check_launch("k_ids_init");
-    if (rc != SDN_OK) return rc;
-    hipLaunchKernelGGL(k_ids_pass_a, dim3(chunks), dim3(ID_THREADS), 0, st, scene, disparity, first, HW, W, table, ws + ID_WS_HI);
-    if ((rc = check_launch("k_ids_pass_a")) != SDN_OK) return rc;
-    hipLaunchKernelGGL(k_ids_select, dim3(ID_OBJS), dim3(64), 0, st, table, ws + ID_WS_HI, ws + ID_WS_SEL);
-    if ((rc = check_launch("k_ids_select")) != SDN_OK) return rc;
-    hipLaunchKernelGGL(k_ids_pass_b, dim3(chunks), dim3(ID_THREADS), 0, st, scene, disparity, first, HW, ws + ID_WS_SEL, ws + ID_WS_LO);
-    if ((rc = check_launch("k_ids_pass_b")) != SDN_OK) return rc;
-    hipLaunchKernelGGL(k_ids_pick, dim3(ID_OBJS), dim3(64), 0, st, table, ws + ID_WS_SEL, ws + ID_WS_LO);
-    return check_launch("k_ids_pick");
+    return ids_chain(
+        ID_OBJS, table, static_cast<int32_t*>(workspace), st,
+        [&](int32_t* hi) {
+            hipLaunchKernelGGL(k_ids_pass_a, dim3(chunks), dim3(ID_THREADS), 0, st, scene, disparity, first, HW, W, table, hi);
+            return check_launch("k_ids_pass_a");
+        },
+        [&](const int32_t* sel, int32_t* lo) {
+            hipLaunchKernelGGL(k_ids_pass_b, dim3(chunks), dim3(ID_THREADS), 0, st, scene, disparity, first, HW, sel, lo);
+            return check_launch("k_ids_pass_b");
+        });
+}
+
+SDN_API int sdn_train_id_stats_workspace_bytes(int B, size_t* out)
+{
+    if (!out || B < 1 || B > 65535) return fail(SDN_EINVAL, "sdn_train_id_stats_workspace_bytes: bad arguments");
+    *out = (size_t)B * ID_WS_PER_ROW * sizeof(int32_t);
+    return SDN_OK;
+}
+
+SDN_API int sdn_train_id_stats(const int32_t* items, int B, long max_pixels, int32_t* table, void* workspace, sdnStream stream)
+{
+    if (!items || !table || !workspace) return fail(SDN_EINVAL, "sdn_train_id_stats: null pointer");
+    if (B < 1 || B > 65535 || max_pixels < 1 || max_pixels > INT_MAX - ID_CHUNK) return fail(SDN_EINVAL, "sdn_train_id_stats: bad sizes");
+    if ((reinterpret_cast<uintptr_t>(workspace) & 15) || (reinterpret_cast<uintptr_t>(table) & 3) || (reinterpret_cast<uintptr_t>(items) & 7))
+        return fail(SDN_EINVAL, "sdn_train_id_stats: the workspace must be aligned to 16 bytes, the items to 8 and the table to 4");
+    hipStream_t st = (hipStream_t)stream;
+    const IdItem* rec = reinterpret_cast<const IdItem*>(items);
+    const dim3 grid(cdiv(max_pixels, ID_CHUNK), (unsigned)B);
+    if (debug_checks()) {   // the precondition 0 .. 65535; synchronous
+        int bad = 0;
+        if (int rc = debug_count("sdn_train_id_stats", st, &bad,
+                                 [&](int* flag) { hipLaunchKernelGGL(k_tid_range, grid, dim3(ID_THREADS), 0, st, rec, flag); }))
+            return rc;
+        if (bad) return fail(SDN_EINVAL, "sdn_train_id_stats: %d disparity values lie outside 0 .. 65535 (16-bit maps only)", bad);
+    }
+    return ids_chain(
+        B, table, static_cast<int32_t*>(workspace), st,
+        [&](int32_t* hi) {
+            hipLaunchKernelGGL(k_tid_pass_a, grid, dim3(ID_THREADS), 0, st, rec, table, hi);
+            return check_launch("k_tid_pass_a");
+        },
+        [&](const int32_t* sel, int32_t* lo) {
+            hipLaunchKernelGGL(k_tid_pass_b, grid, dim3(ID_THREADS), 0, st, rec, sel, lo);
+            return check_launch("k_tid_pass_b");
+        });
 }
 
 SDN_API int sdn_scene_id_planes(const int32_t* scene, const int32_t* disparity, const int32_t* ids, const int32_t* thr, int n, int H,

@@ -4,6 +4,8 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
+#include <cstring>
 
 #include "../../include/sdn_hip.h"
 
@@ -30,6 +32,29 @@ inline int check_launch(const char* what)
 }
 
 inline unsigned cdiv(long a, long b) { return (unsigned)((a + b - 1) / b); }
+
+// SDN_DEBUG_CHECKS=1 in the environment: the entry points that state a precondition on device data count its violations
+inline bool debug_checks()
+{
+    const char* e = getenv("SDN_DEBUG_CHECKS");
+    return e && !strcmp(e, "1");
+}
+
+// The host side of such a count, synchronous: a cleared int on the device, `launch(flag)` issues the counting kernel on `st`,
+// the count comes back in *bad and the int is freed.  `who` is the entry point's name in the refusal.
+template <class Launch>
+inline int debug_count(const char* who, hipStream_t st, int* bad, Launch launch)
+{
+    int* flag = nullptr;
+    if (hipMalloc(&flag, sizeof(int)) != hipSuccess || hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess)
+        return fail(SDN_ELAUNCH, "%s: no memory for the debug check", who);
+    launch(flag);
+    hipError_t e = hipMemcpyAsync(bad, flag, sizeof(int), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(flag);
+    if (e != hipSuccess) return fail(SDN_ELAUNCH, "%s: debug check: %s", who, hipGetErrorString(e));
+    return SDN_OK;
+}
 
 // Opt-in launch timing for bench.py's roofline figures (timing.hip).  A TimedLaunch brackets the kernel launches issued
 // during its lifetime with a hipEvent pair on the launch stream and files the pair, with the algorithmic work of the

@@ -162,10 +162,7 @@ __global__ __launch_bounds__(SEGC_THREADS) void k_segm_colors(const uint8_t* __r
             code[2] = (int)((w1 >> 16) | ((w2 & 0xffu) << 16));
             code[3] = (int)(w2 >> 8);
         } else {
-            for (int j = 0; j < have; j++) {
-                const uint8_t* s = scene + 3 * (p0 + j);
-                code[j] = (int)s[0] | ((int)s[1] << 8) | ((int)s[2] << 16);
-            }
+            for (int j = 0; j < have; j++) code[j] = code24(scene + 3 * (p0 + j));
         }
         int lab[4] = {0, 0, 0, 0}, miss = 0;
         for (int j = 0; j < 4; j++) {

@@ -16,7 +16,9 @@
 //                        is the table label of the scene pixel (ytab[rate y + rate / 2], flip(xtab[rate x + rate / 2])) - 1
 //                        where both indices lie inside the item, -1 elsewhere.  A colour outside the table (the reference
 //                        raises KeyError) gives -1 and is counted, one integer atomic per wave.
-// The colour arithmetic is train_items_common.h's.  Compiled without FMA contraction.
+// The colour arithmetic is train_items_common.h's, and so are the body of the luma kernel (ti_luma_body) and the image kernel's band
+// scheme up to and including the horizontal pass (ti_band_body), both shared with training_item.hip; the vertical pass, BGR,
+// Normalize and the padding (sgt_pixel) are this kernel's own.  Compiled without FMA contraction.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -29,6 +31,8 @@
 namespace sdn {
 
 static_assert(SGT_THREADS == TI_THREADS && SGT_BITS == TI_BITS, "the wave helpers and the fixed point of train_items_common.h");
+static_assert(SGT_SRC_PIXELS == TI_SRC_PIXELS && SGT_PLANE_BYTES == TI_PLANE_BYTES && SGT_STAT_PIXELS == TI_STAT_PIXELS,
+              "the tiles of ti_luma_body and ti_band_body");
 static_assert(3 * (SGT_SRC_PIXELS + SGT_PLANE_BYTES) <= 48 * 1024, "three workgroups per CU");
 
 struct SegTrainParams {
@@ -48,39 +52,11 @@ __device__ __forceinline__ SegTrainItem sgt_item(const SegTrainParams& A, int b)
     return reinterpret_cast<const SegTrainItem*>(A.T)[b];
 }
 
-// the jitter's fields as ti_jitter reads them
-__device__ __forceinline__ TrainItem sgt_jitter_item(const SegTrainItem& it)
-{
-    TrainItem j;
-    j.frame = 0; j.code = 0; j.near_off = 0; j.near_cnt = 0; j.pad0 = 0; j.pad1 = 0;
-    j.nops = it.nops; j.order = it.order; j.fb = it.fb; j.fc = it.fc; j.fs = it.fs; j.hue = it.hue;
-    return j;
-}
-
 __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_luma(const SegTrainParams A)
 {
     __shared__ int s_part[TI_WAVES];
-    const int tid = threadIdx.x, b = blockIdx.y;
-    const TrainItem ji = sgt_jitter_item(sgt_item(A, b));
-    const int at = ti_contrast_at(ji);
-    if (at < 0) return;   // uniform over the workgroup
-    const int total = A.H * A.W;
-    const int i0 = blockIdx.x * SGT_STAT_PIXELS, i1 = min(i0 + SGT_STAT_PIXELS, total);
-    const uint8_t* f = A.frames + (size_t)b * total * 3;
-    int acc = 0;   // at most 8 pixels of 255 per thread
-    for (int i = i0 + tid; i < i1; i += SGT_THREADS) {
-        int r = f[3 * (size_t)i], g = f[3 * (size_t)i + 1], bl = f[3 * (size_t)i + 2];
-        ti_jitter(ji, at, 0, r, g, bl);
-        acc += ti_luma(r, g, bl);
-    }
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        int sum = 0;
-        for (int w = 0; w < TI_WAVES; w++) sum += s_part[w];
-        A.partial[(size_t)b * A.nblk + blockIdx.x] = sum;
-    }
+    const int b = blockIdx.y, total = A.H * A.W;
+    ti_luma_body(sgt_item(A, b), A.frames + (size_t)b * total * 3, total, A.partial + (size_t)b * A.nblk, s_part);
 }
 
 // the finished pixel (y, x) of output channel ch: the vertical pass over colour plane 2 - ch (RGB to BGR, :152), then Normalize
@@ -112,80 +88,14 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_image(const SegTrain
     const int H = A.H, W = A.W, Hb = A.Hb, Wb = A.Wb;
     if (r0 >= Hb) return;
     const SegTrainItem it = sgt_item(A, b);
-    const TrainItem ji = sgt_jitter_item(it);
     if (blockIdx.x == 0 && tid == 0) A.unknown[b] = 0;   // k_segm_train_labels, next in the stream, counts into it
     const int r1 = min(r0 + SGT_BAND, Hb);
     const int rh = min(r1, it.h);   // the rows r0 .. rh - 1 hold pixels
-    // the launcher checked the host's copy of the tables; every branch below is uniform over the workgroup
-    if (it.w < 1 || it.w > SGT_PLANE_BYTES || W > SGT_SRC_PIXELS) return;
-
-    int ybase = 0, rows = 1;
-    if (rh > r0) {
-        int grey = 0;
-        if (ti_contrast_at(ji) >= 0) {   // int(mean(L) + 0.5) = (2 sum + n) / (2 n) in integers; the sum is below 2^21 * 255
-            int acc = 0;
-            for (int i = tid; i < A.nblk; i += SGT_THREADS) acc += A.partial[(size_t)b * A.nblk + i];
-            acc = wave_sum(acc);
-            if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-            __syncthreads();
-            long long sum = 0;
-            for (int w = 0; w < TI_WAVES; w++) sum += s_part[w];
-            const long long cnt = (long long)H * W;
-            grey = (int)((2 * sum + cnt) / (2 * cnt));
-        }
-        const int w = it.w;
-        const int cap = SGT_PLANE_BYTES / w;
-        if (it.yksize == 0) {
-            ybase = r0;
-            rows = rh - r0;
-        } else {
-            const int32_t* yb = A.T + it.yb;
-            int lo = INT_MAX, hi = 0;
-            for (int y = r0; y < rh; y++) {
-                lo = min(lo, yb[2 * y]);
-                hi = max(hi, yb[2 * y] + yb[2 * y + 1]);
-            }
-            ybase = lo;
-            rows = hi - lo;
-        }
-        ybase = min(max(ybase, 0), H - 1);
-        rows = max(1, min(min(rows, H - ybase), cap));
-        const int32_t* xb = A.T + it.xb;
-        const int32_t* xk = A.T + it.xk;
-        const int xksize = it.xksize;
-        const int per = SGT_SRC_PIXELS / W;   // whole frame rows staged per pass
-        const uint8_t* frame = A.frames + (size_t)b * H * W * 3;
-        for (int c0 = 0; c0 < rows; c0 += per) {
-            const int cn = min(per, rows - c0);
-            // stage: the frame rows ybase + c0 .. + cn, mirrored when flipped, jittered once per pixel
-            for (int i = tid; i < cn * W; i += SGT_THREADS) {
-                const int ry = i / W, sx = i - ry * W;
-                const int sy = min(ybase + c0 + ry, H - 1), fx = it.flip ? W - 1 - sx : sx;
-                const uint8_t* p = frame + ((size_t)sy * W + fx) * 3;
-                int cr = p[0], cg = p[1], cb = p[2];
-                ti_jitter(ji, ji.nops, grey, cr, cg, cb);
-                s_src[i] = (uint8_t)cr;
-                s_src[SGT_SRC_PIXELS + i] = (uint8_t)cg;
-                s_src[2 * SGT_SRC_PIXELS + i] = (uint8_t)cb;
-            }
-            __syncthreads();
-            // horizontal pass out of the staged rows, rounded to uint8 as Pillow stores them; a copy when Pillow skips it
-            for (int i = tid; i < 3 * cn * w; i += SGT_THREADS) {
-                const int ch = i / (cn * w), j = i - ch * (cn * w);
-                const int ry = j / w, x = j - ry * w;
-                const uint8_t* row = s_src + ch * SGT_SRC_PIXELS + ry * W;
-                int v;
-                if (xksize == 0) {
-                    v = row[min(x, W - 1)];
-                } else {
-                    const int x0 = max(xb[2 * x], 0), xc = min(xb[2 * x + 1], xksize);
-                    v = ti_resample_byte(row, 1, x0, xc, W - 1, xk + x * xksize);
-                }
-                s_rows[ch * SGT_PLANE_BYTES + (c0 + ry) * w + x] = (uint8_t)v;
-            }
-            __syncthreads();
-        }
-    }
+    // the band's source rows, staged mirrored when the item is flipped, and the horizontal pass (train_items_common.h)
+    int ybase, rows;
+    if (!ti_band_body(it, A.T, A.frames + (size_t)b * H * W * 3, H, W, it.w, r0, rh, it.flip != 0, A.partial + (size_t)b * A.nblk, A.nblk,
+                      s_src, s_rows, s_part, ybase, rows))
+        return;
 
     // vertical pass, BGR, Normalize, and the zeros of the padding: every element of the band's rows is written
     float* out = A.img + (size_t)b * 3 * Hb * Wb;
@@ -233,8 +143,7 @@ __global__ __launch_bounds__(SGT_THREADS) void k_segm_train_labels(const SegTrai
             const int fy = min(max(A.T[it.yn + sy], 0), A.H - 1);
             int fx = min(max(A.T[it.xn + sx], 0), A.W - 1);
             if (it.flip) fx = A.W - 1 - fx;
-            const uint8_t* s = A.scenes + (((size_t)b * A.H + fy) * A.W + fx) * 3;
-            const int code = (int)s[0] | ((int)s[1] << 8) | ((int)s[2] << 16);
+            const int code = code24(A.scenes + (((size_t)b * A.H + fy) * A.W + fx) * 3);
             const int k = seg_find(s_codes, K, code);
             if (k < 0) miss = 1;
             else lab = s_labels[k] - 1;

@@ -46,48 +46,6 @@ struct TrainParams {
     float *images, *masks, *ignores;
 };
 
-// ---- the window's pixels as crop_square returns them ---------------------------------------------------------------------------
-// 0: beyond the padded image (PIL's crop gives 0), 1: padding (the fill value), 2: inside the frame, *p its offset in a plane
-__device__ __forceinline__ int ti_where(const TrainParams& A, const TrainWin& o, int wy, int wx, size_t* p)
-{
-    const int fy = o.oy + wy, fx = o.ox + wx;
-    if (fx >= o.xlim || fy >= o.ylim) return 0;
-    if ((unsigned)fy >= (unsigned)A.H || (unsigned)fx >= (unsigned)A.W) return 1;
-    *p = (size_t)fy * A.W + fx;
-    return 2;
-}
-
-__device__ __forceinline__ void ti_raw_rgb(const TrainParams& A, const TrainWin& o, const TrainItem& it, int wy, int wx, int& r,
-                                           int& g, int& b)
-{
-    size_t p = 0;
-    const int w = ti_where(A, o, wy, wx, &p);
-    if (w < 2) {
-        r = g = b = w ? 127 : 0;
-        return;
-    }
-    const size_t HW = (size_t)A.H * A.W;
-    const uint8_t* f = A.frames + (size_t)it.frame * 3 * HW + p;
-    r = f[0];
-    g = f[HW];
-    b = f[2 * HW];
-}
-
-// kind 1: the mask byte, kind 2: the ignore byte np.uint8(255 * count)
-__device__ __forceinline__ int ti_map_byte(const TrainParams& A, const TrainWin& o, const TrainItem& it, int kind, int wy, int wx)
-{
-    size_t p = 0;
-    const int w = ti_where(A, o, wy, wx, &p);
-    if (w < 2) return (w == 1 && kind == 2) ? 255 : 0;
-    const uint8_t* s = A.scenes + ((size_t)it.frame * A.H * A.W + p) * 3;
-    const int c = (int)s[0] | ((int)s[1] << 8) | ((int)s[2] << 16);
-    if (kind == 1) return c == it.code ? 255 : 0;
-    int count = 0;
-    const uint8_t* nc = A.nearer + 3 * (size_t)it.near_off;
-    for (int k = 0; k < it.near_cnt; k++) count += (c == ((int)nc[3 * k] | ((int)nc[3 * k + 1] << 8) | ((int)nc[3 * k + 2] << 16))) ? 1 : 0;
-    return (255 * count) & 255;
-}
-
 // ---- rois ------------------------------------------------------------------------------------------------------------------
 __global__ void k_train_rois_init(int32_t* table, int B)
 {
@@ -138,8 +96,17 @@ struct TrainSrc {
     const TrainParams& A;
     const TrainWin& o;
     const TrainItem& it;
-    __device__ __forceinline__ void rgb(int wy, int wx, int& r, int& g, int& b) const { ti_raw_rgb(A, o, it, wy, wx, r, g, b); }
-    __device__ __forceinline__ int map_byte(int kind, int wy, int wx) const { return ti_map_byte(A, o, it, kind, wy, wx); }
+    __device__ __forceinline__ void rgb(int wy, int wx, int& r, int& g, int& b) const
+    {
+        ti_raw_rgb(o, A.frames + (size_t)it.frame * 3 * A.H * A.W, A.H, A.W, wy, wx, r, g, b);
+    }
+    __device__ __forceinline__ int map_byte(int kind, int wy, int wx) const
+    {
+        size_t p = 0;
+        const int v = ti_map_outside(o, A.H, A.W, kind, wy, wx, &p);
+        if (v >= 0) return v;
+        return ti_code_byte(A.scenes + (size_t)it.frame * A.H * A.W * 3, p, kind, it.code, A.nearer + 3 * (size_t)it.near_off, it.near_cnt);
+    }
     __device__ __forceinline__ float mean(int ch) const { return A.mean[ch]; }
     __device__ __forceinline__ float stdev(int ch) const { return A.std[ch]; }
 };

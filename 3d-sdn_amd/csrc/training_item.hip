@@ -4,10 +4,11 @@
 //
 // The parameter block (training_item_check.h: TriPlan and the tables it names) is built on the host from the frame's SIZE alone and
 // uploaded in one copy; nothing is read back.  A training item is three launches on the caller's stream, four with a contrast op:
-//   k_tri_luma    only when contrast is among the jitter's ops: partial sums of L, one per 2048 pixels, no atomics (k_segm_train_luma).
-//   k_tri_image   a workgroup owns a band of four rows of the PADDED image, three channels.  The band scheme is k_segm_train_image's:
+//   k_tri_luma    only when contrast is among the jitter's ops: partial sums of L, one per 2048 pixels, no atomics (ti_luma_body of
+//                 train_items_common.h, shared with k_segm_train_luma).
+//   k_tri_image   a workgroup owns a band of four rows of the PADDED image, three channels.  The band scheme is shared with k_segm_train_image (ti_band_body):
 //                 the frame rows the band needs are staged through LDS with the jitter applied once per source pixel, Pillow's
-//                 horizontal pass goes into bytes in LDS, the vertical pass reads them.  The zero padding is placed first and the
+//                 horizontal pass goes into bytes in LDS, the vertical pass (tri_pixel, this kernel's own) reads them.  The zero padding is placed first and the
 //                 padded image mirrored then (model.py:1189), so with an odd pad the two sides differ.  The value is a look-up in
 //                 the host's table fp32(fp64(byte) - MEAN_PIXEL[c]); a padding pixel is the table's entry of 0.  Its first workgroup
 //                 resets the box accumulators and `bad` for the launches behind it.
@@ -34,6 +35,8 @@
 namespace sdn {
 
 static_assert(TRI_THREADS == TI_THREADS && SGT_BITS == TI_BITS, "the wave helpers and the fixed point of train_items_common.h");
+static_assert(SGT_SRC_PIXELS == TI_SRC_PIXELS && SGT_PLANE_BYTES == TI_PLANE_BYTES && SGT_STAT_PIXELS == TI_STAT_PIXELS,
+              "the tiles of ti_luma_body and ti_band_body");
 static_assert(TRI_MAX_BOXES <= TRI_THREADS && 2 * 64 <= TRI_THREADS && TRI_MAX_MINI <= 64, "a lane per instance; a wave per axis of the coefficients");
 
 struct TriArgs {
@@ -57,40 +60,12 @@ struct TriArgs {
 
 __device__ __forceinline__ TriPlan tri_plan(const TriArgs& A) { return *reinterpret_cast<const TriPlan*>(A.P); }
 
-// the jitter's fields as ti_jitter reads them
-__device__ __forceinline__ TrainItem tri_jitter_item(const TriPlan& p)
-{
-    TrainItem j;
-    j.frame = 0; j.code = 0; j.near_off = 0; j.near_cnt = 0; j.pad0 = 0; j.pad1 = 0;
-    j.nops = p.nops; j.order = p.order; j.fb = p.fb; j.fc = p.fc; j.fs = p.fs; j.hue = p.hue;
-    return j;
-}
-
 __global__ __launch_bounds__(TRI_THREADS) void k_tri_luma(const TriArgs A)
 {
     __shared__ int s_part[TI_WAVES];
-    const int tid = threadIdx.x, b = blockIdx.y;
     const TriPlan pl = tri_plan(A);
-    const TrainItem ji = tri_jitter_item(pl);
-    const int at = ti_contrast_at(ji);
-    if (at < 0) return;   // uniform over the workgroup
-    const int total = pl.H * pl.W;
-    const int i0 = blockIdx.x * SGT_STAT_PIXELS, i1 = min(i0 + SGT_STAT_PIXELS, total);
-    const uint8_t* f = A.frames + (size_t)b * total * 3;
-    int acc = 0;   // at most 8 pixels of 255 per thread
-    for (int i = i0 + tid; i < i1; i += TRI_THREADS) {
-        int r = f[3 * (size_t)i], g = f[3 * (size_t)i + 1], bl = f[3 * (size_t)i + 2];
-        ti_jitter(ji, at, 0, r, g, bl);
-        acc += ti_luma(r, g, bl);
-    }
-    acc = wave_sum(acc);
-    if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) {
-        int sum = 0;
-        for (int w = 0; w < TI_WAVES; w++) sum += s_part[w];
-        A.partial[(size_t)b * A.nblk + blockIdx.x] = sum;
-    }
+    const int b = blockIdx.y, total = pl.H * pl.W;
+    ti_luma_body(pl, A.frames + (size_t)b * total * 3, total, A.partial + (size_t)b * A.nblk, s_part);
 }
 
 // the molded pixel (Y, X) of channel ch of the padded, mirrored image
@@ -130,75 +105,13 @@ __global__ __launch_bounds__(TRI_THREADS) void k_tri_image(const TriArgs A)
         }
         if (tid == 0) *A.bad = 0;
     }
-    const TrainItem ji = tri_jitter_item(pl);
     const int Y1 = min(Y0 + TRI_BAND, M);
     const int r0 = max(Y0 - pl.top, 0), rh = min(Y1 - pl.top, pl.oh);   // the resized rows r0 .. rh - 1 hold pixels
-    // the launcher checked the host's copy of the block; every branch below is uniform over the workgroup
-    const int w = pl.ow;
-    if (w < 1 || w > SGT_PLANE_BYTES || W > SGT_SRC_PIXELS) return;
-
-    int ybase = 0, rows = 1;
-    if (rh > r0) {
-        int grey = 0;
-        if (ti_contrast_at(ji) >= 0) {   // int(mean(L) + 0.5) = (2 sum + n) / (2 n) in integers; the sum is below 2^21 * 255
-            int acc = 0;
-            for (int i = tid; i < A.nblk; i += TRI_THREADS) acc += A.partial[(size_t)b * A.nblk + i];
-            acc = wave_sum(acc);
-            if ((tid & 63) == 0) s_part[tid >> 6] = acc;
-            __syncthreads();
-            long long sum = 0;
-            for (int k = 0; k < TI_WAVES; k++) sum += s_part[k];
-            const long long cnt = (long long)H * W;
-            grey = (int)((2 * sum + cnt) / (2 * cnt));
-        }
-        const int cap = SGT_PLANE_BYTES / w;
-        if (pl.yksize == 0) {
-            ybase = r0;
-            rows = rh - r0;
-        } else {
-            const int32_t* yb = A.P + pl.yb;
-            int lo = INT_MAX, hi = 0;
-            for (int y = r0; y < rh; y++) {
-                lo = min(lo, yb[2 * y]);
-                hi = max(hi, yb[2 * y] + yb[2 * y + 1]);
-            }
-            ybase = lo;
-            rows = hi - lo;
-        }
-        ybase = min(max(ybase, 0), H - 1);
-        rows = max(1, min(min(rows, H - ybase), cap));
-        const int32_t* xb = A.P + pl.xb;
-        const int32_t* xk = A.P + pl.xk;
-        const int xksize = pl.xksize;
-        const int per = SGT_SRC_PIXELS / W;   // whole frame rows staged per pass
-        const uint8_t* frame = A.frames + (size_t)b * H * W * 3;
-        for (int c0 = 0; c0 < rows; c0 += per) {
-            const int cn = min(per, rows - c0);
-            // stage: the frame rows ybase + c0 .. + cn, jittered once per pixel
-            for (int i = tid; i < cn * W; i += TRI_THREADS) {
-                const int ry = i / W, sx = i - ry * W;
-                const int sy = min(ybase + c0 + ry, H - 1);
-                const uint8_t* p = frame + ((size_t)sy * W + sx) * 3;
-                int cr = p[0], cg = p[1], cb = p[2];
-                ti_jitter(ji, ji.nops, grey, cr, cg, cb);
-                s_src[i] = (uint8_t)cr;
-                s_src[SGT_SRC_PIXELS + i] = (uint8_t)cg;
-                s_src[2 * SGT_SRC_PIXELS + i] = (uint8_t)cb;
-            }
-            __syncthreads();
-            // horizontal pass out of the staged rows, rounded to uint8 as Pillow stores them; a copy when Pillow skips it
-            for (int i = tid; i < 3 * cn * w; i += TRI_THREADS) {
-                const int ch = i / (cn * w), j = i - ch * (cn * w);
-                const int ry = j / w, x = j - ry * w;
-                const uint8_t* row = s_src + ch * SGT_SRC_PIXELS + ry * W;
-                int v;
-                if (xksize == 0) v = row[min(x, W - 1)];
-                else v = ti_resample_byte(row, 1, max(xb[2 * x], 0), min(xb[2 * x + 1], xksize), W - 1, xk + x * xksize);
-                s_rows[ch * SGT_PLANE_BYTES + (c0 + ry) * w + x] = (uint8_t)v;
-            }
-            __syncthreads();
-        }
-    }
+    // the band's source rows, staged as they lie (tri_pixel mirrors the PADDED image), and the horizontal pass (train_items_common.h)
+    int ybase, rows;
+    if (!ti_band_body(pl, A.P, A.frames + (size_t)b * H * W * 3, H, W, pl.ow, r0, rh, false, A.partial + (size_t)b * A.nblk, A.nblk, s_src,
+                      s_rows, s_part, ybase, rows))
+        return;
 
     // vertical pass, the mirror, the mean and the padding: every element of the band's rows is written
     float* out = A.image + (size_t)b * 3 * M * M;

@@ -29,7 +29,8 @@ def planes(g, tag, what):
 
 
 def find_rank(hist, rank):
-    """(bin, rank inside the bin) of the element of zero-based rank `rank` in a histogram, as k_ids_select / k_ids_pick scan it"""
+    """(bin, rank inside the bin) of the element of zero-based rank `rank` in a histogram, as k_ids_select / k_ids_pick scan it
+    (for sdn_scene_id_stats and sdn_train_id_stats alike)"""
     incl = np.cumsum(hist.astype(np.int64))
     b = int(np.searchsorted(incl, rank, side='right'))
     assert b < len(hist), 'rank beyond the histogram'

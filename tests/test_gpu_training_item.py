@@ -112,9 +112,11 @@ def test_load_image_gt_returns_the_references_five(gold):
 
 
 @pytest.mark.parametrize('order', [[pillow.HUE, pillow.BRIGHTNESS, pillow.SATURATION], [pillow.SATURATION, pillow.CONTRAST, pillow.HUE, pillow.BRIGHTNESS],
-                                   [pillow.CONTRAST]])
+                                   [pillow.CONTRAST], [pillow.BRIGHTNESS, pillow.CONTRAST]])
 @pytest.mark.parametrize('name', ['down', 'same'])
 def test_the_jitter_cases_equal_the_util(gold, name, order):
+    """The last order puts an op that moves the mean of L in front of contrast: saturation, in the second, blends around L and keeps
+    it, so a luma sum taken before the preceding ops gives the same grey there."""
     cfg, p = u.case_config(gold, name), name + '_'
     jitter = (order, (1.3, 0.7, 1.4), 37)
     item = ti.training_item(*case_inputs(gold, name), cfg, flip=1, jitter=jitter)

@@ -86,6 +86,47 @@ def test_the_check_headers_share_one_macro_pair_one_alignment_test_and_one_round
             assert CHECK in reach(name), name
 
 
+def test_the_device_loaders_hold_one_copy_of_the_select_the_debug_count_and_the_pillow_bodies():
+    everything = ''.join(SOURCES.values())
+    # one switch, one host helper around a counting kernel, used by the three entry points that state a precondition
+    assert everything.count('getenv("SDN_DEBUG_CHECKS")') == 1 and 'getenv("SDN_DEBUG_CHECKS")' in SOURCES['sdn_common.h']
+    assert everything.count('hipFree(flag)') == 1
+    for name, calls in (('scene_crops.hip', 1), ('scene_ids.hip', 2)):
+        assert SOURCES[name].count('debug_count("sdn_') == calls and 'debug_checks()' in SOURCES[name], name
+    # the jitter is read from the item rows themselves: nothing fills a TrainItem field by field
+    assert 'j.frame = 0' not in everything and not re.search(r'\bTrainItem \w+jitter\w*\(', everything)
+    assert 'template <class Item>\n__device__ __forceinline__ void ti_jitter(const Item& it,' in SOURCES['train_items_common.h']
+    # the radix select calls the rank search from exactly one select kernel and one pick kernel, and both entry points launch those
+    loaders = {name: SOURCES[name] for name in ('scene_ids.hip', 'train_hybrid.hip', 'train_items.hip', 'segm_train.hip', 'training_item.hip')}
+    callers = sorted((name, kernel) for name, text in loaders.items() for kernel, body in kernels(text) if 'ids_find(' in body)
+    assert callers == [('scene_ids.hip', 'k_ids_pick'), ('scene_ids.hip', 'k_ids_select')]
+    assert sum(text.count('ids_find(') for text in loaders.values()) == 4   # two ranks in each
+    assert not re.search(r'\bk_tid_(init|select|pick)\b', everything)
+    assert len(re.findall(r'return ids_chain\(', SOURCES['scene_ids.hip'])) == 2
+    # the packed colour of a scene pixel and the accumulation of a Pillow pass are each written once
+    assert everything.count('| ((int)s[1] << 8) |') == 1 and 'code24(const uint8_t* s)' in SOURCES[DEVICE]
+    for name in ('train_items_common.h', 'train_items.hip', 'train_hybrid.hip', 'segm_train.hip', 'segm_tail.hip'):
+        assert 'code24(' in reach_text(name), name
+    common = SOURCES['train_items_common.h']
+    assert len(re.findall(r'int acc = 1 << \(TI_BITS - 1\)', everything)) == 1 and len(re.findall(r'acc >> TI_BITS', everything)) == 1
+    assert common.index('int acc = 1 << (TI_BITS - 1)') < common.index('ti_resample_byte(', common.index('ti_crops_body('))
+    # one luma partial and one band body, called by the two image loaders
+    for name, calls in (('segm_train.hip', ('ti_luma_body(', 'ti_band_body(')), ('training_item.hip', ('ti_luma_body(', 'ti_band_body('))):
+        for call in calls:
+            assert SOURCES[name].count(call) == 1, (name, call)
+        assert 'ti_jitter(' not in SOURCES[name] and 'SRC_PIXELS + i] =' not in SOURCES[name], name
+
+
+def kernels(text):
+    """(name, body) of every __global__ function of a source"""
+    return [(m.group(1), text[m.end():].split('\n}\n')[0]) for m in re.finditer(r'__global__[^\n;{]*\bvoid (\w+)\(', text)]
+
+
+def reach_text(name):
+    """a source with the csrc headers it reaches"""
+    return SOURCES[name] + ''.join(SOURCES[n] for n in reach(name))
+
+
 def reach(name, seen=None):
     """the csrc headers `name` includes, directly or through others"""
     seen = set() if seen is None else seen
