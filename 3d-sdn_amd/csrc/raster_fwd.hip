@@ -18,7 +18,9 @@
 //                  instead) in four runs, one per wave.  A wave rasterises 64 faces at a time, one fetched per lane: the
 //                  clipped candidate boxes of up to 256 pixels (nearly all of an 85k-face mesh: a few pixels each) form ONE
 //                  stream of (face, pixel) candidates, of which every pass of the wave takes 64 consecutive ones whichever
-//                  faces they belong to (the owner's coordinates come through ds_bpermute); a pass only runs the edge tests and
+//                  faces they belong to (the owner's coordinates come through ds_bpermute; a stream position is a run of STREAM_G = 4
+//                  adjacent pixels of one row, so the look-up, the operands and the row half of the edge tests are paid once per
+//                  run: 228 -> 208 us per launch on the CAD-like frame); a pass only runs the edge tests and
 //                  queues the covered pixels in LDS; every 64 queued hits are shaded by all 64 lanes (barycentrics,
 //                  perspective depth) and resolved with ds_min_u64 on the packed key ord(depth) << 32 | face_index;
 //                  larger faces are broadcast (v_readlane) and walked by row spans.  r02: 658 -> 399 us per 16-object frame.
@@ -59,6 +61,15 @@ constexpr int FREC = 13;        // floats per face record of a batch (odd: conse
 #endif
 constexpr int FLAT_MAX = SDN_LAB_FLAT_MAX;  // clipped candidate boxes up to this many pixels join the batch's candidate stream; larger ones are walked by row spans
 static_assert(FLAT_MAX >= 1 && FLAT_MAX <= 256, "a batch's stream holds at most 64 * 256 candidates: 14 bits of start, at most 256 passes (the marks are u16, 0xffff = none)");
+#ifndef SDN_LAB_STREAM_GROUP
+#define SDN_LAB_STREAM_GROUP 4   // (sweep, k_raster_tiles us per launch, two interleaved runs each, parent = one pixel per position before the run form:
+                                 // cad_like parent 229.4 / 228.3, 1: 226.3 / 231.3, 2: 212.0 / 214.3, 4: 207.3 / 208.4; car_like parent 156.8 / 155.3,
+                                 // 1: 157.2 / 159.8, 2: 141.8 / 144.2, 4: 142.6 / 141.1; the six real templates together parent 273.6 / 281.8, 2: 269.8 / 264.0,
+                                 // 4: 256.3 / 257.8; all three fit 80 registers without scratch in <false, 2>; profiles/raster_pixel_runs.md)
+#endif
+constexpr int STREAM_G = SDN_LAB_STREAM_GROUP;  // a position of the candidate stream is a RUN of this many horizontally adjacent pixels of one row of one face's clipped box
+static_assert(STREAM_G == 1 || STREAM_G == 2 || STREAM_G == 4, "a run is 1, 2 or 4 pixels (its column count is a shift of the box width)");
+constexpr int STREAM_SH = STREAM_G == 4 ? 2 : STREAM_G == 2 ? 1 : 0;
 #ifndef SDN_LAB_HIZ_MIN_LIST
 #define SDN_LAB_HIZ_MIN_LIST 257   // = every tile on the long-list path (> 64 * NWAVE entries); us per launch cad_like / real templates / car_like:
                                    // off 289 / 490 / 196, always 291 / 325 / 214, >= 2048: 290 / 490 / 196, 1024: 288 / 343 / 195, 512: 275 / 317 / 195, 256: 266 / 313 / 196
@@ -942,8 +953,17 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
         // instructions as 6 more permutes, and the same floats).  A pass is about 66 vector-ALU and 15 LDS instructions in the ISA (the
         // ten permutes, mark, read, two table reads, the depth read), queue append included; the linear wave-shared walk was ~45 per pass
         // plus ~40 per box.
+        // Pixel runs: a stream position is a RUN of STREAM_G horizontally adjacent pixels of one row of a box (ceil(w / G) * h
+        // positions per face; prefix sum, marks and look-up count runs).  Everything above but the x half of the edge tests depends
+        // on (face, row) only, and so do inside_ndc's three (yp - ya)(xb - xa) products: a lane pays them once (inside_ndc_row) and
+        // runs the per-pixel half (inside_ndc_px, the same expressions), the depth compare and the queue append for each pixel of
+        // its run that lies inside the box -- a masked pixel touches no LDS.  ISA per pass, vector-ALU / LDS / scalar: one pixel per
+        // position 65 / 16 / 36, G = 2 about 89 / 18 / 57, G = 4 about 131 / 24 / 110 (the path without a drain, summed over its basic
+        // blocks) for 0.53 x and 0.29 x the positions on the bench meshes.
         {
-            const int fa = area_l <= FLAT_MAX ? area_l : 0;
+            // (membership is decided by the PIXEL area, so the row-span boxes are the same for every STREAM_G)
+            const int gw_l = ((lw > 0 ? lw : 1) + STREAM_G - 1) >> STREAM_SH;   // runs per row
+            const int fa = (area_l > 0 && area_l <= FLAT_MAX) ? gw_l * lh : 0;  // runs of this face: <= its pixels <= FLAT_MAX
             int incl = fa;
 #pragma unroll
             for (int d = 1; d < 64; d <<= 1) {
@@ -951,11 +971,12 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
                 if (lane >= d) incl += o;
             }
             const int T = __builtin_amdgcn_readlane(incl, 63);
-            // what a candidate needs of its owner besides the six coordinates: box origin and width (tile pixels), stream start
-            // (< 64 * 256: 14 bits; the sign bit marks a lane without candidates); 1 / width
+            // what a run needs of its owner besides the six coordinates: box origin and PIXEL width (tile pixels; the width masks the
+            // short last run of a row), stream start in runs (< 64 * 256: 14 bits; the sign bit marks a lane without candidates);
+            // 1 / (runs per row)
             const int box_l = ((lx0 - X0) & 31) | (((ly0 - Y0) & 31) << 5) | (((lw - 1) & 31) << 10) | ((incl - fa) << 15) |
                               (fa > 0 ? 0 : (int)0x80000000);
-            const float rw_l = 1.0f / (float)(lw > 0 ? lw : 1);
+            const float rw_l = 1.0f / (float)gw_l;
             // the flat faces in lane order are the stream's faces in start order: rank r's lane (the other lanes fill the ranks behind)
             const unsigned long long fm = __ballot(fa > 0);
             const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(fm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fm, 0u));
@@ -987,20 +1008,43 @@ __global__ __launch_bounds__(NTHR, 6) void k_raster_tiles(const FwdParams P)   /
 #pragma unroll
                 for (int kk = 0; kk < 9; kk++)
                     f[kk] = (kk % 3 == 2) ? 0.0f : __int_as_float(__builtin_amdgcn_ds_bpermute(a4, __float_as_int(f_l[kk])));
-                bool hit = false;
-                int px = 0, py = 0;
+                // what the run's pixels share: its row, its first column, how many of its STREAM_G pixels lie inside the box
+                // (0: no run for this lane), the three row products and the three (yb - ya) of inside_ndc
+                // (kept as the queue entry of the run's first pixel, slot | px0 << 6 | py << 11: entry >> 6 is that pixel's index in
+                // the tile and the next pixel's entry is 1 << 6 further -- two registers less than px0, py and the slot apart)
+                uint32_t e0 = (uint32_t)s;
+                int left = 0;
+                float lhs[3] = {0.0f, 0.0f, 0.0f}, dy[3] = {0.0f, 0.0f, 0.0f};
                 if (base + lane < T) {
+                    // runs per row gw <= 32 and i < gw * rows <= 256: (gw, i) is one of the (width, index) pairs this decode is
+                    // used on with one pixel per position
+                    const int lwm1 = (box >> 10) & 31;
+                    const int gw = (lwm1 >> STREAM_SH) + 1;
                     const int i = base + lane - (box >> 15);
                     const int yy = (int)(((float)i + 0.5f) * rw);
-                    const int xx = i - yy * (((box >> 10) & 31) + 1);
-                    px = (box & 31) + xx;
-                    py = ((box >> 5) & 31) + yy;
-                    if constexpr (COUNT) n_cand++;
-                    hit = inside_ndc(f, xtab[px], ytab[py]);
-                    if constexpr (COUNT) n_in += hit ? 1u : 0u;
-                    if (hit) hit = !behind(zc, px, py);
+                    const int xx = (i - yy * gw) << STREAM_SH;
+                    const int px0 = (box & 31) + xx;
+                    const int py = ((box >> 5) & 31) + yy;
+                    left = lwm1 + 1 - xx;   // >= 1; px0 + j stays inside the box, hence inside the tile, for j < left
+                    e0 |= ((uint32_t)px0 << 6) | ((uint32_t)py << 11);
+                    inside_ndc_row(f, ytab[py], lhs, dy);
                 }
-                push_hits(hit, (uint32_t)s | ((uint32_t)px << 6) | ((uint32_t)py << 11));
+                // first every pixel's tests (their table and depth reads are in flight together), then the queue
+                const int pidx = (int)(e0 >> 6);   // py * TS + px0
+                bool hit[STREAM_G];
+#pragma unroll
+                for (int j = 0; j < STREAM_G; j++) {
+                    hit[j] = false;
+                    if (j < left) {   // (a masked pixel reads neither xtab nor zbuf)
+                        if constexpr (COUNT) n_cand++;
+                        hit[j] = inside_ndc_px(f, lhs, dy, xtab[(pidx & 31) + j]);
+                        if constexpr (COUNT) n_in += hit[j] ? 1u : 0u;
+                        if (hit[j]) hit[j] = !(zc > zhi[2 * (pidx + j) + 1]);   // (behind(), by tile index)
+                    }
+                }
+                // (at most 63 entries wait before a call and a call adds at most 64: the queue's 128 hold them)
+#pragma unroll
+                for (int j = 0; j < STREAM_G; j++) push_hits(hit[j], e0 + ((uint32_t)j << 6));
             }
         }
         tick(c_small);

@@ -69,6 +69,27 @@ __device__ __forceinline__ bool inside_ndc(const float f[9], float xp, float yp)
     return true;
 }
 
+// inside_ndc for several pixels of ONE row: the three left-hand products and the three (yb - ya) factors depend on the face and
+// the row only (inside_ndc_row), the rest on the pixel (inside_ndc_px).  The same expressions as inside_ndc, operand for operand
+// (the same `<`, no fusion: callers are built with -ffp-contract=off), so a (face, pixel) pair gets the same answer either way.
+__device__ __forceinline__ void inside_ndc_row(const float f[9], float yp, float lhs[3], float dy[3])
+{
+    lhs[0] = (yp - f[1]) * (f[3] - f[0]);
+    lhs[1] = (yp - f[4]) * (f[6] - f[3]);
+    lhs[2] = (yp - f[7]) * (f[0] - f[6]);
+    dy[0] = f[4] - f[1];
+    dy[1] = f[7] - f[4];
+    dy[2] = f[1] - f[7];
+}
+
+__device__ __forceinline__ bool inside_ndc_px(const float f[9], const float lhs[3], const float dy[3], float xp)
+{
+    if (lhs[0] < (xp - f[0]) * dy[0]) return false;
+    if (lhs[1] < (xp - f[3]) * dy[1]) return false;
+    if (lhs[2] < (xp - f[6]) * dy[2]) return false;
+    return true;
+}
+
 // rasterize.py:316-328 -- clamp through fmax/fmin (NaN loses), renormalise
 __device__ __forceinline__ void bary_weights(const float inv[9], int xi, int yi, float w[3])
 {
